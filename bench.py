@@ -60,6 +60,12 @@ def parse():
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the secondary legs (BASELINE.json configs[1] radar-BEV batch 4 and configs[4] bf16 batch 8)")
     ap.add_argument("--leg", action="store_true", help=argparse.SUPPRESS)      # child mode of secondary_legs(): compact line
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: the conv roofline (serialized "
+                         "step), the loss window, eval-forward latency, the decoder rooflines, the CPU baseline and the "
+                         "secondary legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
     return ap.parse_args()
 
 
@@ -208,7 +214,7 @@ def secondary_legs(args):
     import subprocess
     out = {}
     for name, flags in SECONDARY_LEGS.items():
-        cmd = [sys.executable, os.path.abspath(__file__), "--leg", "--steps", "12", "--warmup", "5", "--latency-reps", "30",
+        cmd = [sys.executable, os.path.abspath(__file__), "--leg", "--full", "--steps", "12", "--warmup", "5", "--latency-reps", "30",
                "--no-cpu-baseline"] + flags
         t0 = time.perf_counter()
         try:
@@ -256,6 +262,23 @@ def exchange_diagnostics(trainer, bucket_trace, last_step_ms):
                   "stream: start = issue point, end = an event on a helper stream that waits for the work)"}
 
 
+def runtime_state(trainer):
+    """Fields the trainer settles while it runs (queue probe, host-pacing decision), read when the line is completed: at the end
+    of the timed steps in a plain run, at the end of the run with --full."""
+    return {
+        "hardware_queues": {"distinct_besides_main": trainer.model.__dict__.get("_queues_found"),
+                            "placement": os.environ.get("DPFT_STREAM_PLACEMENT", "probe"),
+                            "note": "views and the camera's weight-gradient stream sit on probed, distinct hardware queues "
+                                    "(dpft_stream_set); collectives: " + {"side": "in order on the camera's weight-gradient stream",
+                                                                        "front": "in order on the last view's stream",
+                                                                        "pg": "the process group's own stream",
+                                                                        "own": "a dedicated stream"}.get(
+                                        trainer.comm_placement, trainer.comm_placement)},
+        "host_pacing": dict(mode=trainer.pace_host, **{k: v for k, v in trainer.__dict__.get("_pace_state", {}).items()
+                                                       if k in ("decided", "host_ms", "gpu_ms")}),
+    }
+
+
 def decoder_runner(m, data):
     """-> (run, feats): ``run()`` = exactly one dpft_decoder_forward_f32 call (the fused inference decoder of one
     IMPFusion.forward) on the encoded pyramids of ``data``.  Also used by tools/decoder_only.py for the PMC passes."""
@@ -273,6 +296,34 @@ def decoder_runner(m, data):
             raise RuntimeError("the fused HIP decoder is not active for this configuration")
         fd.prepare(vb, shp, proj, c0, flags)
     return fd.launch, feats
+
+
+DUMP_PARAM_SAMPLES = 1 << 22        # 16 MiB of float32 parameter values
+
+
+def dump_outputs(out_dir, loss, losses, model):
+    """What the last timed step computed, as ``out_dir/<name>.npy``: ``train_step``'s return values -- ``loss.npy`` and
+    ``loss_<term>.npy`` for every term of the set loss, float64 -- and ``params_sample.npy``, the parameters AdamW wrote in
+    that step, float32: a fixed sample of up to 2^22 positions of the flat concatenation of ``model.parameters()`` (logical
+    layout, registration order), drawn from numpy's ``default_rng(0)`` and sorted.  The inputs are seeded, so two builds
+    run with the same arguments can be compared file for file -- with a tolerance: the fp32 atomics of the training decoder's
+    backward make the trajectory differ from run to run (two runs of 5 + 20 steps on one MI355X: loss terms up to 3.5e-3
+    relative, parameters within 9e-4 of the largest magnitude and 1e-2 relative L2), and the spread grows with the number of
+    steps."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().double().cpu().numpy())
+    for k, v in losses.items():
+        np.save(os.path.join(out_dir, f"loss_{k}.npy"), torch.as_tensor(v).detach().double().cpu().numpy())
+    params = list(model.parameters())
+    offs = np.concatenate(([0], np.cumsum([p.numel() for p in params])))
+    idx = np.unique(np.random.default_rng(0).integers(0, int(offs[-1]), size=min(DUMP_PARAM_SAMPLES, int(offs[-1]))))
+    chunks = []
+    for p, start, lo, hi in zip(params, offs[:-1], np.searchsorted(idx, offs[:-1]), np.searchsorted(idx, offs[1:])):
+        if hi > lo:
+            sel = torch.from_numpy(idx[lo:hi] - start).to(p.device)
+            chunks.append(p.detach().reshape(-1)[sel].float().cpu())
+    np.save(os.path.join(out_dir, "params_sample.npy"), torch.cat(chunks).numpy())
 
 
 def main():
@@ -358,7 +409,7 @@ def main():
     for i in range(args.steps):
         if collective and i == args.steps - 1:
             trainer.reducer.trace_begin()      # per-bucket ready / start / end marks of the LAST timed step (~3 event records per bucket)
-        loss, _ = trainer.train_step(data, labels)
+        loss, losses = trainer.train_step(data, labels)
         marks[i + 1].record()
     sync()
     elapsed = time.perf_counter() - t0
@@ -373,6 +424,58 @@ def main():
         elapsed = float(t.item())
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * B * args.steps / elapsed
+    line = None
+    if rank == 0:
+        line = {
+            "metric": f"training samples/sec (K-Radar C+R, bs{B}/GPU)", "value": value, "unit": "samples/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+            "step_ms_first8": [round(v, 2) for v in step_ms_order[:8]],      # (in order: the steps right behind the sync at the start)
+            "step_ms_min": step_ms[0], "step_ms_median": step_ms[len(step_ms) // 2], "step_ms_max": step_ms[-1],
+            "step_ms_is": "rank 0, per step: HIP events on the main stream at every step boundary of the timed region",
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "config": {"workload": f"{args.config}.json full C+R dual-perspective fusion train step, batch {B}/GPU "
+                                   "(camera 512x910x3 ResNet-101, radar BEV 256x107x6 + front 37x107x6 ResNet-50, "
+                                   "FPN->16ch, IMPFusion 4 it x 3 views, Hungarian set loss, AdamW)",
+                       "global_batch": world * B, "parallelism": f"dp{world}",
+                       "precision": {"f32": "fp32 (reference arithmetic; fp32 tensors and fp32 results everywhere)" +
+                                            ("" if args.no_split else ": the big multi-tap conv GEMMs form each fp32 product from six exact bf16 "
+                                             "term products on the bf16 matrix cores (3 x bf16 split, fp32 accumulation), the rest runs on "
+                                             "the fp32 MFMA"),
+                                     "bf16": "mixed (BASELINE.json configs[4]): bf16 operands / fp32 accumulation in the conv GEMMs; "
+                                             "activations of the large (camera) encoder bodies stored as bf16 in HBM, BatchNorm "
+                                             "statistics / accumulators / master weights / decoder / loss / AdamW fp32",
+                                     "f32x3": "experimental: fp32 conv operands as three bf16 terms, six term products "
+                                              "on the bf16 matrix cores, fp32 accumulation"}[args.dtype]},
+            "step_definition": "zero_grad, forward, Hungarian set loss, backward, bucketed all-reduce, AdamW; the per-step "
+                               "eval_fn of the reference's loop (trainer.py:134-136) is not part of the timed step",
+            "rccl_ranks": world, "collectives_forced": bool(args.force_collectives and world == 1),
+            "collective_op": (trainer.reducer.collective_op + (" (one rank: avg == sum; RCCL's one-rank AVG is a pre-multiply pass "
+                              "over every bucket, +0.8 ms/step, DPFT_COLLECTIVE_OP=avg)" if world == 1 else ""))
+                             if trainer.collective else None,
+            "exposed_allreduce_ms": exposed_ms,
+            "exposed_allreduce_is": "last timed step: from the point the rank's CURRENT (main) stream has finished its own "
+                                    "backward work to the completion of the last bucket's collective, bracketed by events on "
+                                    "that stream; collectives of view-stream buckets that finish earlier are not in it",
+            "dp_bucket_mb": trainer.bucket_mb,
+            "dp_exchange": exchange_diagnostics(trainer, bucket_trace, step_ms_order[-1] if step_ms_order else None) if collective else None,
+            "dp_comm_dtype": trainer.comm_dtype,
+            "loss": float(loss),
+            **runtime_state(trainer),
+            "host_pacing_is": "DataParallelTrainer._pace: the host waits for the GPU to reach the decoder's forward graph before it enqueues "
+                              "the backward; 'auto' does so when four measured steps say the host's own period is < 0.8 x the GPU's",
+            "full": bool(args.full),
+            "full_is": "--full adds the conv and decoder rooflines, the loss window, eval-forward latency, the CPU baseline and the "
+                       "secondary legs, all measured after the timed steps",
+        }
+        if args.dump_outputs:           # before anything else runs a step: the values of the LAST timed step
+            dump_outputs(args.dump_outputs, loss, losses, trainer.model)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line))
+        if collective:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- roofline of the dominant kernel family: fp32 MFMA implicit-GEMM convolutions --------------
     roof, per_kind = None, {}
@@ -669,55 +772,11 @@ def main():
         secondary = secondary_legs(args)
 
     if rank == 0:
-        line = {
-            "metric": f"training samples/sec (K-Radar C+R, bs{B}/GPU)", "value": value, "unit": "samples/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "step_ms_first8": [round(v, 2) for v in step_ms_order[:8]],      # (in order: the steps right behind the sync at the start)
-            "step_ms_min": step_ms[0], "step_ms_median": step_ms[len(step_ms) // 2], "step_ms_max": step_ms[-1],
-            "step_ms_is": "rank 0, per step: HIP events on the main stream at every step boundary of the timed region",
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": f"{args.config}.json full C+R dual-perspective fusion train step, batch {B}/GPU "
-                                   "(camera 512x910x3 ResNet-101, radar BEV 256x107x6 + front 37x107x6 ResNet-50, "
-                                   "FPN->16ch, IMPFusion 4 it x 3 views, Hungarian set loss, AdamW)",
-                       "global_batch": world * B, "parallelism": f"dp{world}",
-                       "precision": {"f32": "fp32 (reference arithmetic; fp32 tensors and fp32 results everywhere)" +
-                                            ("" if args.no_split else ": the big multi-tap conv GEMMs form each fp32 product from six exact bf16 "
-                                             "term products on the bf16 matrix cores (3 x bf16 split, fp32 accumulation), the rest runs on "
-                                             "the fp32 MFMA"),
-                                     "bf16": "mixed (BASELINE.json configs[4]): bf16 operands / fp32 accumulation in the conv GEMMs; "
-                                             "activations of the large (camera) encoder bodies stored as bf16 in HBM, BatchNorm "
-                                             "statistics / accumulators / master weights / decoder / loss / AdamW fp32",
-                                     "f32x3": "experimental: fp32 conv operands as three bf16 terms, six term products "
-                                              "on the bf16 matrix cores, fp32 accumulation"}[args.dtype]},
+        line.update(runtime_state(trainer))
+        line.update({
             "fwd_ms_per_frame": fwd_mean / B, "fwd_ms_per_batch": fwd_mean, "fwd_ms_std": fwd_std,
             "fwd_ms_batch1": fwd1_mean, "fwd_ms_batch1_std": fwd1_std,
             "fwd_protocol": f"10 warm-up + {args.latency_reps} event-timed eval forwards of one batch (evaluator.py:109-125)",
-            "step_definition": "zero_grad, forward, Hungarian set loss, backward, bucketed all-reduce, AdamW; the per-step "
-                               "eval_fn of the reference's loop (trainer.py:134-136) is not part of the timed step",
-            "rccl_ranks": world, "collectives_forced": bool(args.force_collectives and world == 1),
-            "collective_op": (trainer.reducer.collective_op + (" (one rank: avg == sum; RCCL's one-rank AVG is a pre-multiply pass "
-                              "over every bucket, +0.8 ms/step, DPFT_COLLECTIVE_OP=avg)" if world == 1 else ""))
-                             if trainer.collective else None,
-            "exposed_allreduce_ms": exposed_ms,
-            "exposed_allreduce_is": "last timed step: from the point the rank's CURRENT (main) stream has finished its own "
-                                    "backward work to the completion of the last bucket's collective, bracketed by events on "
-                                    "that stream; collectives of view-stream buckets that finish earlier are not in it",
-            "dp_bucket_mb": trainer.bucket_mb,
-            "dp_exchange": exchange_diagnostics(trainer, bucket_trace, step_ms_order[-1] if step_ms_order else None) if collective else None,
-            "hardware_queues": {"distinct_besides_main": trainer.model.__dict__.get("_queues_found"),
-                                "placement": os.environ.get("DPFT_STREAM_PLACEMENT", "probe"),
-                                "note": "views and the camera's weight-gradient stream sit on probed, distinct hardware queues "
-                                        "(dpft_stream_set); collectives: " + {"side": "in order on the camera's weight-gradient stream",
-                                                                            "front": "in order on the last view's stream",
-                                                                            "pg": "the process group's own stream",
-                                                                            "own": "a dedicated stream"}.get(
-                                            trainer.comm_placement, trainer.comm_placement)},
-            "dp_comm_dtype": trainer.comm_dtype,
-            "loss": float(loss),
-            "host_pacing": dict(mode=trainer.pace_host, **{k: v for k, v in trainer.__dict__.get("_pace_state", {}).items()
-                                                           if k in ("decided", "host_ms", "gpu_ms")}),
-            "host_pacing_is": "DataParallelTrainer._pace: the host waits for the GPU to reach the decoder's forward graph before it enqueues "
-                              "the backward; 'auto' does so when four measured steps say the host's own period is < 0.8 x the GPU's",
             "loss_window_us": loss_window_us,
             "loss_window_is": "median GPU time from the end of the matcher's cost kernel to the start of the decoder's backward graph "
                               "(assignment kernel -- one wavefront per sample, no host round trip --, criterion + gradient kernels; "
@@ -730,7 +789,7 @@ def main():
                             "mixed precision, batch 8): this script as a child process per leg, after and outside the headline's timed "
                             "region -- 5 warm-up + 12 timed steps, barrier + device sync on both sides; frac = that leg's conv family "
                             "against its own peak (fp32 MFMA 157.3 TF | bf16 2500 TF), serialized-step event brackets",
-        }
+        })
         print(json.dumps(line))
     if collective:
         dist.barrier()                    # rank 0 is still measuring (decoder roofline) when the others get here

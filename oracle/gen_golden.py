@@ -442,6 +442,65 @@ def gen_msda_init():
     np.savez_compressed(os.path.join(OUT, "msda_init.npz"), **_np(out))
 
 
+def gen_reference_digests():
+    """SHA-256 digests (oracle/digests.py) of what the reference's own code and files give, for the cross-checks of
+    tests/test_host.py and tests/test_kradar_dataset.py -- reference_digests.json holds digests and seeds only:
+      configs         the compared sections of its five config files
+      fuser           state-dict layout of its IMPFusion (kradar) and the deterministic sampling-offset bias
+      dprt_tree       its DPRT module tree without backbones / necks (kradar, fuser dropout 0.05), as torch.save pickles it
+      kradar_dataset  every tensor of its KRadarDataset items on the seeded file tree of tests/test_kradar_dataset.py,
+                      per sample folder with the np.random seed of the draw, plain and with modality dropout"""
+    import importlib.util
+    import tempfile
+    from dprt.models.dprt import DPRT
+    from dprt.models.embeddings import build_embedding
+    from dprt.models.fusers import build_fuser
+    from dprt.models.heads import build_head
+    from dprt.models.queries import build_querent
+    from oracle import digests as D
+    cfg_dir = os.path.dirname(CFG)
+    out = {"configs": {}}
+    for name in ("kradar", "kradar_camera_mono", "kradar_radar_bev", "kradar_radar_front", "kradar_radar"):
+        out["configs"][name] = D.config_digest(json.load(open(os.path.join(cfg_dir, name + ".json"))))
+    cfg = json.load(open(CFG))
+    comp, m = cfg["computing"], cfg["model"]
+    fuser = build_fuser(m["fuser"]["name"], dict(comp | m["fuser"]), head=build_head(m["head"]["name"], dict(comp | m["head"])))
+    sd = fuser.state_dict()
+    bias = "mpfusion.fusion0.ml_fusion_layers.ms_deform_attn0.ms_deform_attn.sampling_offsets.bias"
+    out["fuser"] = {"state_layout": D.state_layout_digest(sd), "sampling_offsets_bias": D.tensor_digest(sd[bias])}
+    m["fuser"]["dropout"] = 0.05
+    head = build_head(m["head"]["name"], dict(comp | m["head"]))
+    ref = DPRT(inputs=m["inputs"], skiplinks=m["skiplinks"],
+               embeddings={v: build_embedding(e["name"], dict(comp | e)) for v, e in m["embeddings"].items()},
+               querent=build_querent(m["querent"]["name"], dict(comp | m["querent"])),
+               fuser=build_fuser(m["fuser"]["name"], dict(comp | m["fuser"]), head=head), head=head)
+    out["dprt_tree"] = D.module_tree_digest(ref.eval(), skip=("backbones", "necks"))
+
+    spec = importlib.util.spec_from_file_location("kradar_dataset_test", os.path.join(os.path.dirname(OUT), "test_kradar_dataset.py"))
+    tk = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tk)
+    from dpft_amd.data.kradar import read_image_hwc
+    import dprt.datasets.kradar.dataset as ref_ds
+    ref_ds.read_image = lambda path: read_image_hwc(path).movedim(-1, 0)      # torchvision.io.read_image: (C, H, W) uint8
+    fov_t = {k: torch.tensor(v) for k, v in tk.FOV.items()}
+    out["kradar_dataset"] = {"tree_seed": 3}
+    with tempfile.TemporaryDirectory() as root:
+        tk._write_tree(root, seed=3)
+        for tag, kw, seed0 in (("plain", {}, 0), ("dropout", {"camera_dropout": 0.4, "radar_dropout": 0.4}, 100)):
+            ds = ref_ds.KRadarDataset(root, **kw, **tk.KW)
+            ds.fov = fov_t
+            rows = []
+            for i in range(len(ds)):
+                np.random.seed(seed0 + i)
+                item, label = ds[i]
+                folder = os.path.relpath(os.path.dirname(ds.dataset_paths[i]["description"]), root).replace(os.sep, "/")
+                rows.append({"folder": folder, "seed": seed0 + i, "item": [[k] + D.tensor_digest(v) for k, v in item.items()],
+                             "label": [[k] + D.tensor_digest(v) for k, v in label.items()]})
+            out["kradar_dataset"][tag] = rows
+    with open(os.path.join(OUT, "reference_digests.json"), "w") as f:
+        json.dump(out, f, indent=1)
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["assign"]:                 # only the round-2 fixture (keeps the other files byte-identical)
         ref_import.install()
@@ -450,5 +509,9 @@ if __name__ == "__main__":
         ref_import.install()
         os.makedirs(OUT, exist_ok=True)
         gen_msda_init()
+    elif sys.argv[1:] == ["reference_digests"]:    # only the digests of the reference cross-checks
+        ref_import.install()
+        os.makedirs(OUT, exist_ok=True)
+        gen_reference_digests()
     else:
         main()

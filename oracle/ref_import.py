@@ -7,8 +7,8 @@ tensorboard, deepspeed).  This module registers *namespace-only* stand-ins in
 oracle's own grid_sample core -- the reference ships no CPU core) and
 puts /root/reference/src on ``sys.path``.  Nothing is copied; nothing is written there.
 
-Only ``oracle/gen_golden.py`` and the ``-m "not gpu"`` reference cross-check tests use it,
-and they skip when /root/reference is absent (the GPU box).
+Only ``oracle/gen_golden.py`` uses it; the tests read the fixtures it writes under tests/golden/
+and need no reference checkout.
 """
 from __future__ import annotations
 

@@ -1,5 +1,5 @@
 """Every distinct convolution problem of the bench step (kradar.json, batch 4: the rows of the committed per-shape conv
-table profiles/r0N_conv_table_fp32.txt, written by `DPFT_CONV_TABLE=... python bench.py`) -- forward, data gradient and
+table profiles/r0N_conv_table_fp32.txt, written by `DPFT_CONV_TABLE=... python bench.py --full`) -- forward, data gradient and
 weight gradient through the C-ABI vs fp64 F.conv2d, in the operand forms the ResNet plan / FPN use them with (BN + ReLU
 operand prologue, BN tile statistics, bias, accumulating data gradient).  Pins the dispatch table (tile shape, split-K,
 parity-class / K-split / thin-input variants are chosen by problem size) at the sizes the headline number is measured on."""

@@ -8,7 +8,13 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+
+
+@pytest.fixture(scope="module")
+def golden_digests():
+    """Digests of what the reference's own code and files give (oracle/gen_golden.py reference_digests)."""
+    with open(os.path.join(ROOT, "tests", "golden", "reference_digests.json")) as f:
+        return json.load(f)
 
 
 def test_cabi_exports_every_declared_symbol():
@@ -87,41 +93,40 @@ def test_state_dict_layout_matches_reference_naming():
     assert w.permute(0, 2, 3, 1).is_contiguous()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
-def test_fuser_state_dict_identical_to_reference():
-    from oracle import ref_import
-    ref_import.install()
-    from dprt.models.fusers import build_fuser as ref_build_fuser
-    from dprt.models.heads import build_head as ref_build_head
+def test_fuser_state_dict_identical_to_reference(golden_digests):
+    """Same state-dict layout (names, order, shapes) as the reference's IMPFusion, and the same deterministic
+    initialisation (ring-pattern sampling offsets) -- against digests of the reference's own module
+    (tests/golden/reference_digests.json, oracle/gen_golden.py reference_digests)."""
+    from oracle import digests as D
     from dpft_amd.configs import load_config
     from dpft_amd.models.fusers import build_fuser
     from dpft_amd.models.heads import build_head
     cfg = load_config("kradar")
     comp, m = cfg["computing"], cfg["model"]
     ours = build_fuser(m["fuser"]["name"], dict(comp | m["fuser"]), head=build_head(m["head"]["name"], dict(comp | m["head"])))
-    ref = ref_build_fuser(m["fuser"]["name"], dict(comp | m["fuser"]),
-                          head=ref_build_head(m["head"]["name"], dict(comp | m["head"])))
-    a, b = ours.state_dict(), ref.state_dict()
-    assert list(a.keys()) == list(b.keys())
-    for k in a:
-        assert a[k].shape == b[k].shape, k
-    # deterministic initialisations agree (ring-pattern sampling offsets, zero attention weights)
+    a, ref = ours.state_dict(), golden_digests["fuser"]
+    # equal layouts: our checkpoint loads into the reference module unchanged (strict load_state_dict)
+    assert D.state_layout_digest(a) == ref["state_layout"]
     k = "mpfusion.fusion0.ml_fusion_layers.ms_deform_attn0.ms_deform_attn.sampling_offsets.bias"
-    assert torch.equal(a[k], b[k])
-    ref.load_state_dict(a)        # our checkpoint loads into the reference module unchanged
+    assert D.tensor_digest(a[k]) == ref["sampling_offsets_bias"]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
 @pytest.mark.parametrize("name", ["kradar", "kradar_camera_mono", "kradar_radar_bev", "kradar_radar_front", "kradar_radar"])
-def test_builtin_configs_equal_reference_jsons(name):
+def test_builtin_configs_equal_reference_jsons(name, tmp_path, golden_digests):
+    """The built-in configs are the reference's config/<name>.json files with the backbone weights names blanked: ours with
+    the weights name put back has the digest of the reference file's compared sections (tests/golden/reference_digests.json),
+    and that file form loads as the reference's file does."""
+    from oracle import digests as D
     from dpft_amd.configs import load_config
     ours = load_config(name)
-    ref = json.load(open(os.path.join(REF, "config", name + ".json")))
+    ref = json.loads(json.dumps(ours))
     for bb in ref["model"]["backbones"].values():
-        bb["weights"] = ""
-    for section in ("computing", "train", "model", "evaluate"):
-        assert ours[section] == ref[section], section
-    path = os.path.join(REF, "config", name + ".json")
+        assert bb["weights"] == ""
+        bb["weights"] = "IMAGENET1K_V2"
+    assert D.config_digest(ref) == golden_digests["configs"][name]
+    path = str(tmp_path / (name + ".json"))
+    with open(path, "w") as f:
+        json.dump(ref, f)
     with pytest.warns(UserWarning, match="RANDOM initialisation"):            # explicit opt-in, never silent (ADVICE r1)
         loaded = load_config(path, offline=True)
     assert loaded["model"] == ours["model"]
@@ -177,16 +182,46 @@ def test_synthetic_batch_contract():
     assert len(lab) == 4 and all(1 <= l["gt_center"].shape[0] <= 8 for l in lab)
 
 
-def _foreign_tree(state_dict, module_path, cls_name):
-    """A module tree whose classes pickle as ``<module_path>.<cls_name>`` (a class path that will NOT be importable when
-    the file is read) holding exactly ``state_dict`` -- the shape of what torch.save(model) writes for the third-party
-    parts (torchvision ResNet / FPN) of a reference checkpoint."""
-    import sys
-    import types
-    mod = sys.modules.get(module_path) or types.ModuleType(module_path)
-    cls = getattr(mod, cls_name, None) or type(cls_name, (torch.nn.Module,), {"__module__": module_path})
-    setattr(mod, cls_name, cls)
-    sys.modules[module_path] = mod
+class _ForeignClasses:
+    """Classes that pickle under class paths which are NOT importable when the file is read (the reference's ``dprt.*``,
+    torchvision's): inside the ``with`` block every module of their dotted paths is a stand-in in ``sys.modules`` (what the
+    pickler looks the class up in), removed again on exit."""
+
+    def __init__(self):
+        self.made, self.saved = {}, {}
+
+    def cls(self, module_path, name):
+        if (module_path, name) not in self.made:
+            self.made[(module_path, name)] = type(name, (torch.nn.Module,), {"__module__": module_path})
+        return self.made[(module_path, name)]
+
+    def __enter__(self):
+        import sys
+        import types
+        for (path, name), cls in self.made.items():
+            parts = path.split(".")
+            for i in range(1, len(parts) + 1):
+                p = ".".join(parts[:i])
+                if p not in self.saved:
+                    self.saved[p] = sys.modules.get(p)
+                    sys.modules[p] = types.ModuleType(p)
+            setattr(sys.modules[path], name, cls)
+        return self
+
+    def __exit__(self, *exc):
+        import sys
+        for p, old in self.saved.items():
+            if old is None:
+                sys.modules.pop(p, None)
+            else:
+                sys.modules[p] = old
+        return False
+
+
+def _foreign_tree(state_dict, classes, module_path, cls_name):
+    """A module tree whose classes pickle as ``<module_path>.<cls_name>`` holding exactly ``state_dict`` -- the shape of what
+    torch.save(model) writes for the third-party parts (torchvision ResNet / FPN) of a reference checkpoint."""
+    cls = classes.cls(module_path, cls_name)
     root = cls()
     for key, t in state_dict.items():
         node, parts = root, key.split(".")
@@ -201,21 +236,35 @@ def _foreign_tree(state_dict, module_path, cls_name):
     return root
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
-def test_load_reads_reference_whole_module_checkpoint(tmp_path):
+def _as_reference_tree(mod, classes, skip=()):
+    """What the reference's own module tree pickles as, made from this package's, which mirrors it class for class and
+    attribute for attribute: every ``dpft_amd.models.X.Y`` becomes ``dprt.models.X.Y``, each module keeps its pickled state
+    minus this package's own caches (``_tables`` / ``_cache``: the reference has none).  The top-level children in ``skip``
+    are left empty.  The test pins the result to the reference's tree by digest."""
+    from collections import OrderedDict
+    cls = type(mod)
+    if cls.__module__.startswith("dpft_amd."):
+        cls = classes.cls("dprt." + cls.__module__[len("dpft_amd."):], cls.__qualname__)
+    st = dict(mod.__getstate__())
+    st.pop("_tables", None)
+    st.pop("_cache", None)
+    obj = cls.__new__(cls)
+    obj.__dict__.update(st)
+    obj.__dict__["_parameters"] = dict(mod._parameters)
+    obj.__dict__["_buffers"] = dict(mod._buffers)
+    obj.__dict__["_modules"] = OrderedDict((k, torch.nn.ModuleDict() if k in skip else _as_reference_tree(c, classes))
+                                           for k, c in mod._modules.items())
+    return obj
+
+
+def test_load_reads_reference_whole_module_checkpoint(tmp_path, golden_digests):
     """f-3 remainder (VERDICT r1 missing #1): ``dpft_amd.models.load`` on a ``torch.save(model)`` file whose classes are
     the REFERENCE's (dprt.models.dprt.DPRT, IMPFusion, MLFusion, MSDeformAttn, LinearDetectionHead, the querent, the
-    embeddings -- built here by the imported reference itself) and torchvision's (class paths that are not importable
-    when the file is read): the rebuilt dpft_amd model has the same hyper-parameters, parameters and buffers."""
-    import sys
+    embeddings -- the reference's module tree, equal by digest to what the reference itself builds) and torchvision's
+    (class paths that are not importable when the file is read): the rebuilt dpft_amd model has the same
+    hyper-parameters, parameters and buffers."""
     from collections import OrderedDict
-    from oracle import ref_import
-    ref_import.install()
-    from dprt.models.dprt import DPRT as RefDPRT
-    from dprt.models.embeddings import build_embedding
-    from dprt.models.fusers import build_fuser
-    from dprt.models.heads import build_head
-    from dprt.models.queries import build_querent
+    from oracle import digests as D
     from dpft_amd.configs import load_config
     from dpft_amd.models import build, load
     cfg = load_config("kradar")
@@ -223,36 +272,25 @@ def test_load_reads_reference_whole_module_checkpoint(tmp_path):
     cfg["model"]["fuser"]["dropout"] = 0.05
     comp, m = cfg["computing"], cfg["model"]
     torch.manual_seed(12)
-    ours = build("dprt", cfg)                                               # source of the third-party tensors
+    ours = build("dprt", cfg)                                               # source of the tensors
     with torch.no_grad():
         for p in ours.parameters():
             p.add_(torch.randn_like(p) * 0.01)
     sd = ours.state_dict()
-    head = build_head(m["head"]["name"], dict(comp | m["head"]))
-    fuser = build_fuser(m["fuser"]["name"], dict(comp | m["fuser"]), head=head)
-    ref = RefDPRT(inputs=m["inputs"], skiplinks=m["skiplinks"],
-                  embeddings={v: build_embedding(e["name"], dict(comp | e)) for v, e in m["embeddings"].items()},
-                  querent=build_querent(m["querent"]["name"], dict(comp | m["querent"])), fuser=fuser, head=head)
-    ref.fuser.load_state_dict({k[len("fuser."):]: v for k, v in sd.items() if k.startswith("fuser.")})
-    ref.head.load_state_dict({k[len("head."):]: v for k, v in sd.items() if k.startswith("head.")})
-    made = []
-    try:
-        for kind, path, cname in (("backbones", "torchvision.models.resnet", "ResNet"),
-                                  ("necks", "torchvision.ops.feature_pyramid_network", "FeaturePyramidNetwork")):
-            made.append(path)
-            holder = torch.nn.ModuleDict()
-            for v in m["inputs"]:
-                pre = f"{kind}.{v}."
-                holder[v] = _foreign_tree(OrderedDict((k[len(pre):], t) for k, t in sd.items() if k.startswith(pre)),
-                                          path, cname)
-            setattr(ref, kind, holder)
-        ref.eval()
-        ckpt = tmp_path / "20240101-120000_checkpoint_0042.pt"
+    classes = _ForeignClasses()
+    ref = _as_reference_tree(ours, classes, skip=("backbones", "necks")).eval()
+    assert D.module_tree_digest(ref, skip=("backbones", "necks")) == golden_digests["dprt_tree"]
+    for kind, path, cname in (("backbones", "torchvision.models.resnet", "ResNet"),
+                              ("necks", "torchvision.ops.feature_pyramid_network", "FeaturePyramidNetwork")):
+        holder = torch.nn.ModuleDict()
+        for v in m["inputs"]:
+            pre = f"{kind}.{v}."
+            holder[v] = _foreign_tree(OrderedDict((k[len(pre):], t) for k, t in sd.items() if k.startswith(pre)),
+                                      classes, path, cname)
+        ref._modules[kind] = holder.eval()
+    ckpt = tmp_path / "20240101-120000_checkpoint_0042.pt"
+    with classes:
         torch.save(ref, str(ckpt))
-    finally:
-        for path in made:
-            if path not in ref_import.STUBS:
-                sys.modules.pop(path, None)
     assert b"dprt.models.fusers.mpfusion" in ckpt.read_bytes() and b"torchvision.models.resnet" in ckpt.read_bytes()
     model, epoch, stamp = load(str(ckpt))
     assert (epoch, stamp) == (42, "20240101-120000")

@@ -1,17 +1,14 @@
 """The K-Radar folder reader (dpft_amd/data/kradar.py) against the reference's own KRadarDataset on the same files.
 
 A small pre-processed tree is written to a temp dir (random JPEG frames, radar maps in dB, calibration matrices, label
-rows incl. boxes outside the field of view); the reference class is imported through oracle/ref_import (its
-``torchvision.io.read_image`` -- torchvision is absent -- bound to the same Pillow decode) and every item is compared
-tensor for tensor, key order included.  The device-transform mode (raw uint8 frame, unscaled maps) is checked against the
+rows incl. boxes outside the field of view); the reference class's items on that tree (its ``torchvision.io.read_image``
+bound to the same Pillow decode) are pinned by digest, tensor for tensor, key order included.  The device-transform mode (raw uint8 frame, unscaled maps) is checked against the
 host mode + the arithmetic of the two transforms."""
 import os
 
 import numpy as np
 import pytest
 import torch
-
-from oracle import ref_import
 
 PIL = pytest.importorskip("PIL")
 
@@ -92,42 +89,25 @@ def test_folder_reader_collates_like_the_reference_loader(tmp_path):
     assert batch["label_to_radar_front_p"].shape == (4, 3, 4) and len(labels) == 4
 
 
-@pytest.mark.skipif(not ref_import.available(), reason="/root/reference is not present")
 def test_folder_reader_equals_the_reference_dataset(tmp_path):
-    """Item for item against src/dprt/datasets/kradar/dataset.py on the same files (no resize: torchvision's is absent)."""
-    from dpft_amd.data.kradar import KRadarFolderDataset, read_image_hwc
-    ref_import.install()
-    import dprt.datasets.kradar.dataset as ref_ds
-    ref_ds.read_image = lambda path: read_image_hwc(path).movedim(-1, 0)      # torchvision.io.read_image: (C, H, W) uint8
-    root = _write_tree(str(tmp_path), seed=3)
-    ref = ref_ds.KRadarDataset(root, **KW)
-    ours = KRadarFolderDataset(root, device_transforms=False, **KW)
-    assert len(ref) == len(ours) == 6
-    fov_t = {k: torch.tensor(v) for k, v in FOV.items()}
-    ref.fov = fov_t
-    # upstream walks the sequences in os.listdir order (file-system dependent), this repo in sorted order (every rank must see
-    # the same index -> sample map): pair the items by their sample folder, and check that both hold the same set
-    where = {os.path.dirname(f["description"]): j for j, f in enumerate(ours.samples)}
-    assert sorted(where) == sorted(os.path.dirname(f["description"]) for f in ref.dataset_paths)
-    for i in range(len(ref)):
-        np.random.seed(i)
-        item_r, label_r = ref[i]
-        np.random.seed(i)
-        item_o, label_o = ours[where[os.path.dirname(ref.dataset_paths[i]["description"])]]
-        assert list(item_r.keys()) == list(item_o.keys())
-        for k in item_r:
-            assert item_r[k].dtype == item_o[k].dtype and torch.equal(item_r[k], item_o[k]), k
-        assert list(label_r.keys()) == list(label_o.keys())
-        for k in label_r:
-            assert torch.equal(label_r[k], label_o[k]), k
-    # the same with a modality dropped, the same random draw
-    ref2 = ref_ds.KRadarDataset(root, camera_dropout=0.4, radar_dropout=0.4, **KW)
-    ref2.fov = fov_t
-    ours2 = KRadarFolderDataset(root, device_transforms=False, camera_dropout=0.4, radar_dropout=0.4, **KW)
-    for i in range(len(ref2)):
-        np.random.seed(100 + i)
-        item_r, _ = ref2[i]
-        np.random.seed(100 + i)
-        item_o, _ = ours2[where[os.path.dirname(ref2.dataset_paths[i]["description"])]]
-        for k in item_r:
-            assert torch.equal(item_r[k], item_o[k]), k
+    """Item for item against src/dprt/datasets/kradar/dataset.py on the same files (no resize: torchvision's is absent):
+    every tensor of every item, in key order, has the digest of the reference's (tests/golden/reference_digests.json,
+    written by oracle/gen_golden.py reference_digests from the reference class on this seeded tree), drawn under the same
+    np.random seed -- plain and with a modality dropped."""
+    import json
+    from oracle import digests as D
+    from dpft_amd.data.kradar import KRadarFolderDataset
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_digests.json")) as f:
+        ref = json.load(f)["kradar_dataset"]
+    root = _write_tree(str(tmp_path), seed=ref["tree_seed"])
+    for tag, kw in (("plain", {}), ("dropout", {"camera_dropout": 0.4, "radar_dropout": 0.4})):
+        ours = KRadarFolderDataset(root, device_transforms=False, **kw, **KW)
+        # upstream walks the sequences in os.listdir order (file-system dependent), this repo in sorted order (every rank must
+        # see the same index -> sample map): pair the items by their sample folder, and check that both hold the same set
+        where = {os.path.relpath(os.path.dirname(f["description"]), root).replace(os.sep, "/"): j for j, f in enumerate(ours.samples)}
+        assert len(ours) == len(ref[tag]) == 6 and sorted(where) == sorted(r["folder"] for r in ref[tag])
+        for r in ref[tag]:
+            np.random.seed(r["seed"])
+            item, label = ours[where[r["folder"]]]
+            assert [[k] + D.tensor_digest(v) for k, v in item.items()] == r["item"], (tag, r["folder"])
+            assert [[k] + D.tensor_digest(v) for k, v in label.items()] == r["label"], (tag, r["folder"])

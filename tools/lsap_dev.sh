@@ -6,7 +6,7 @@ timeout 900 python -m pytest tests/test_gpu_lsap.py -x -q 2>&1 | tail -5
 timeout 1500 python -m pytest tests/test_gpu_trainer.py -x -q 2>&1 | tail -5
 for v in 1 0; do
   echo "== DPFT_LSAP_DEV=$v"
-  DPFT_LSAP_DEV=$v timeout 900 python bench.py --steps 40 --warmup 10 2>/dev/null | grep "^{" | python -c "
+  DPFT_LSAP_DEV=$v timeout 900 python bench.py --full --steps 40 --warmup 10 2>/dev/null | grep "^{" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print({k:d[k] for k in ('value','ms_per_step','loss_window_us','loss_window_assignments','loss')})"

@@ -8,7 +8,7 @@ SERIAL=1 STEPS=10 timeout 600 rocprofv3 --kernel-trace --stats --output-format c
 f=$(find /tmp/q_serial_$TAG -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $OUT/serialized_step_kernel_stats.csv
 python /root/repo/tools/roofline_from_rocprof.py $OUT/serialized_step_kernel_stats.csv 13 > $OUT/roofline_from_rocprof.json
 cd /root/repo
-timeout 600 python bench.py --steps ${STEPS_BENCH:-40} --warmup 10 --no-cpu-baseline --latency-reps 30 > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 python bench.py --full --steps ${STEPS_BENCH:-40} --warmup 10 --no-cpu-baseline --latency-reps 30 > $OUT/bench.json 2> $OUT/bench.err
 python - $OUT <<'PY'
 import json, sys
 o = sys.argv[1]

@@ -1,4 +1,5 @@
 # Round-4 evidence run (one gpurun call).  usage: bash tools/r04_profile.sh  -> gpurun_out/r04_*  (copy into profiles/)
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=/root/repo/gpurun_out/r04p
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
@@ -75,8 +76,8 @@ PY
 # (5) SQ wave-cycle / MFMA-busy breakdown of the conv kernels on the layer-3 problems (one PMC pass)
 bash /root/repo/tools/pmc_conv_sq.sh > $OUT/r04_conv_sq_mfma_busy.txt 2>&1
 # (6) mixed precision (configs[4]): bf16 operands + bf16 activation storage, batch 8 per GPU: bench line + serialized kernel summary
-DPFT_CONV_TABLE=$OUT/r04_conv_table_bf16_b8.txt timeout 600 python /root/repo/bench.py --dtype bf16 --batch 8 --steps 20 --warmup 5 --no-cpu-baseline --latency-reps 50 > $OUT/r04_bench_bf16_b8.json 2> $OUT/r04_bench_bf16_b8.err
-timeout 600 python /root/repo/bench.py --dtype bf16 --batch 4 --steps 20 --warmup 5 --no-cpu-baseline --latency-reps 50 > $OUT/r04_bench_bf16_b4.json 2>> $OUT/r04_bench_bf16_b8.err
+DPFT_CONV_TABLE=$OUT/r04_conv_table_bf16_b8.txt timeout 600 python "$REPO/bench.py" --full --dtype bf16 --batch 8 --steps 20 --warmup 5 --no-cpu-baseline --latency-reps 50 > $OUT/r04_bench_bf16_b8.json 2> $OUT/r04_bench_bf16_b8.err
+timeout 600 python "$REPO/bench.py" --full --dtype bf16 --batch 4 --steps 20 --warmup 5 --no-cpu-baseline --latency-reps 50 > $OUT/r04_bench_bf16_b4.json 2>> $OUT/r04_bench_bf16_b8.err
 for b in 8 4; do
   SERIAL=1 STEPS=10 DTYPE=bf16 BATCH=$b timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_serial16_$b -- python /root/repo/tools/train_only.py </dev/null > $OUT/r04_serial_bf16_b$b.log 2>&1
   f=$(find /tmp/p_serial16_$b -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $OUT/r04_bf16_b${b}_serialized_step_kernel_stats.csv
@@ -119,11 +120,11 @@ PY
 bash /root/repo/tools/radar_prof.sh > $OUT/r04_radar_projection.txt 2>&1
 # (7b) the RCCL path on one rank: forced collectives (line carries rccl_ranks 1, collectives_forced true)
 # (100 timed steps each, plain and forced back to back in the same call)
-timeout 900 python /root/repo/bench.py --gpus 1 --steps 100 --warmup 20 --no-cpu-baseline --latency-reps 20 > $OUT/r04_bench_plain_100steps.json 2> $OUT/r04_bench_forced.err
-timeout 900 python /root/repo/bench.py --gpus 1 --steps 100 --warmup 20 --force-collectives --no-cpu-baseline --latency-reps 20 > $OUT/r04_bench_forced_collectives.json 2>> $OUT/r04_bench_forced.err
+timeout 900 python "$REPO/bench.py" --full --gpus 1 --steps 100 --warmup 20 --no-cpu-baseline --latency-reps 20 > $OUT/r04_bench_plain_100steps.json 2> $OUT/r04_bench_forced.err
+timeout 900 python "$REPO/bench.py" --full --gpus 1 --steps 100 --warmup 20 --force-collectives --no-cpu-baseline --latency-reps 20 > $OUT/r04_bench_forced_collectives.json 2>> $OUT/r04_bench_forced.err
 # (8) the default bench line of this state: the command the driver runs (python bench.py = 100 timed + 20 warm-up steps)
 cd /root/repo
-DPFT_CONV_TABLE=$OUT/r04_conv_table_fp32.txt timeout 900 python bench.py > $OUT/r04_bench.json 2> $OUT/r04_bench.err
+DPFT_CONV_TABLE=$OUT/r04_conv_table_fp32.txt timeout 900 python bench.py --full > $OUT/r04_bench.json 2> $OUT/r04_bench.err
 # (9) loader-in-the-loop rate, frozen-BN / train-mode gradient probe
 timeout 600 python tools/loader_rate.py > $OUT/r04_loader_rate.json 2> $OUT/r04_loader_rate.err
 timeout 900 python tools/grad_gap_probe.py > $OUT/r04_grad_gap_probe_rerun.txt 2> /dev/null      # (profiles/r04_grad_gap_probe.txt also holds the four-other-seeds runs)

@@ -1,4 +1,5 @@
 # Round-5 evidence run (one gpurun call).  usage: bash tools/r05_profile.sh  -> gpurun_out/r05_*  (copy into profiles/)
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=/root/repo/gpurun_out/r05p
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
@@ -75,8 +76,8 @@ PY
 # (5) SQ wave-cycle / MFMA-busy breakdown of the conv kernels on the layer-3 problems (one PMC pass)
 bash /root/repo/tools/pmc_conv_sq.sh > $OUT/r05_conv_sq_mfma_busy.txt 2>&1
 # (6) mixed precision (configs[4]): bf16 operands + bf16 activation storage, batch 8 per GPU: bench line + serialized kernel summary
-DPFT_CONV_TABLE=$OUT/r05_conv_table_bf16_b8.txt timeout 600 python /root/repo/bench.py --dtype bf16 --batch 8 --steps 20 --warmup 5 --no-cpu-baseline --latency-reps 50 > $OUT/r05_bench_bf16_b8.json 2> $OUT/r05_bench_bf16_b8.err
-timeout 600 python /root/repo/bench.py --dtype bf16 --batch 4 --steps 20 --warmup 5 --no-cpu-baseline --latency-reps 50 > $OUT/r05_bench_bf16_b4.json 2>> $OUT/r05_bench_bf16_b8.err
+DPFT_CONV_TABLE=$OUT/r05_conv_table_bf16_b8.txt timeout 600 python "$REPO/bench.py" --full --dtype bf16 --batch 8 --steps 20 --warmup 5 --no-cpu-baseline --latency-reps 50 > $OUT/r05_bench_bf16_b8.json 2> $OUT/r05_bench_bf16_b8.err
+timeout 600 python "$REPO/bench.py" --full --dtype bf16 --batch 4 --steps 20 --warmup 5 --no-cpu-baseline --latency-reps 50 > $OUT/r05_bench_bf16_b4.json 2>> $OUT/r05_bench_bf16_b8.err
 for b in 8 4; do
   SERIAL=1 STEPS=10 DTYPE=bf16 BATCH=$b timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_serial16_$b -- python /root/repo/tools/train_only.py </dev/null > $OUT/r05_serial_bf16_b$b.log 2>&1
   f=$(find /tmp/p_serial16_$b -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $OUT/r05_bf16_b${b}_serialized_step_kernel_stats.csv
@@ -119,14 +120,14 @@ PY
 bash /root/repo/tools/radar_prof.sh > $OUT/r05_radar_projection.txt 2>&1
 # (7b) the RCCL path on one rank: forced collectives (line carries rccl_ranks 1, collectives_forced true)
 # (100 timed steps each, plain and forced back to back in the same call)
-timeout 900 python /root/repo/bench.py --gpus 1 --steps 100 --warmup 20 --no-cpu-baseline --latency-reps 20 > $OUT/r05_bench_plain_100steps.json 2> $OUT/r05_bench_forced.err
-timeout 900 python /root/repo/bench.py --gpus 1 --steps 100 --warmup 20 --force-collectives --no-cpu-baseline --latency-reps 20 > $OUT/r05_bench_forced_collectives.json 2>> $OUT/r05_bench_forced.err
+timeout 900 python "$REPO/bench.py" --full --gpus 1 --steps 100 --warmup 20 --no-cpu-baseline --latency-reps 20 > $OUT/r05_bench_plain_100steps.json 2> $OUT/r05_bench_forced.err
+timeout 900 python "$REPO/bench.py" --full --gpus 1 --steps 100 --warmup 20 --force-collectives --no-cpu-baseline --latency-reps 20 > $OUT/r05_bench_forced_collectives.json 2>> $OUT/r05_bench_forced.err
 # (8) the default bench line of this state: the command the driver runs (python bench.py = 100 timed + 20 warm-up steps)
 cd /root/repo
 # (the driver's own command: python bench.py --steps 20 --warmup 5, CPU leg included)
-DPFT_CONV_TABLE=$OUT/r05_conv_table_fp32.txt timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/r05_bench.json 2> $OUT/r05_bench.err
+DPFT_CONV_TABLE=$OUT/r05_conv_table_fp32.txt timeout 900 python bench.py --full --steps 20 --warmup 5 > $OUT/r05_bench.json 2> $OUT/r05_bench.err
 # (8b) the same without the split kernels (fp32 MFMA everywhere): the round's A/B on one box
-timeout 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-split > $OUT/r05_bench_no_split.json 2> $OUT/r05_bench_no_split.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-split > $OUT/r05_bench_no_split.json 2> $OUT/r05_bench_no_split.err
 # (9) loader-in-the-loop rate, frozen-BN / train-mode gradient probe
 timeout 600 python tools/loader_rate.py > $OUT/r05_loader_rate.json 2> $OUT/r05_loader_rate.err
 timeout 900 python tools/grad_gap_probe.py > $OUT/r05_grad_gap_probe_rerun.txt 2> /dev/null      # (profiles/r05_grad_gap_probe.txt also holds the four-other-seeds runs)
@@ -137,6 +138,6 @@ bash /root/repo/tools/step_vendor_rows.sh > $OUT/r05_step_vendor_rows.txt 2>&1
 FILES=1 timeout 600 python /root/repo/tools/loader_rate.py > /dev/null 2>&1      # (first run on a fresh box: the tree is written, the workers' imports are cold -- 134 vs 152 samples/s)
 FILES=1 timeout 600 python /root/repo/tools/loader_rate.py > $OUT/r05_loader_rate_files.json 2>> $OUT/r05_loader_rate.err
 # (12) the driver's own command under the kernel trace: python bench.py --steps 20 --warmup 5 (CPU leg off: it is host work)
-cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_benchcmd -- python /root/repo/bench.py --steps 20 --warmup 5 --no-cpu-baseline </dev/null > $OUT/r05_bench_cmd_under_rocprof.json 2> $OUT/r05_bench_cmd.err
+cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_benchcmd -- python "$REPO/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline </dev/null > $OUT/r05_bench_cmd_under_rocprof.json 2> $OUT/r05_bench_cmd.err
 f=$(find /tmp/p_benchcmd -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $OUT/r05_bench_cmd_kernel_stats.csv
 cd /root/repo

@@ -2,7 +2,7 @@
 cd /root/repo; export PYTHONUNBUFFERED=1
 O=gpurun_out/r6b; mkdir -p $O
 python -m pytest tests/test_gpu_model.py tests/test_gpu_kernels.py -q -s -m gpu -k "full_size_train_step or halfspace" > $O/parity.txt 2>&1; tail -3 $O/parity.txt
-python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.json
+python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.json
 q() { python bench.py --steps 40 --warmup 10 --no-cpu-baseline --latency-reps 5 2>/dev/null | grep "^{" | tail -n 1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$1', round(d['value'],1), 'mean', round(d['ms_per_step'],2), 'median', round(d['step_ms_median'],2), 'min', round(d['step_ms_min'],2))"; }
 for i in 1 2 3; do

@@ -2,7 +2,7 @@
 # vs 2 (lib_v0: 190 VGPRs), isolated shape + whole step; (b) tile choice of the layer-3 1x1 forward / data-gradient shapes
 cd /root/repo; export PYTHONUNBUFFERED=1
 cp dpft_amd/libdpft_hip.so /tmp/lib_keep.so
-step() { python bench.py --steps 40 --warmup 10 --no-cpu-baseline --latency-reps 5 2>/dev/null | grep "^{" | tail -n 1 | python -c "
+step() { python bench.py --full --steps 40 --warmup 10 --no-cpu-baseline --latency-reps 5 2>/dev/null | grep "^{" | tail -n 1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$1', round(d['value'],1), 'mean', round(d['ms_per_step'],2), 'median', round(d['step_ms_median'],2), 'min', round(d['step_ms_min'],2), 'conv_ms', round(d['roofline']['conv_ms_per_step'],2))"; }
 for rep in 1 2; do for v in 0 3; do
   cp tools/ab/lib_v$v.so dpft_amd/libdpft_hip.so

@@ -72,13 +72,13 @@ print(json.dumps({k: dout.get(k) for k in ("traffic_bytes_per_forward", "forward
 PY
 # (5) the driver's own command (CPU leg + secondary legs included) with the per-shape conv table + the family flops of the step
 cd /root/repo
-DPFT_CONV_TABLE=$OUT/r06_conv_table_fp32.txt timeout 1200 python bench.py --steps 20 --warmup 5 > $OUT/r06_bench.json 2> $OUT/r06_bench.err
+DPFT_CONV_TABLE=$OUT/r06_conv_table_fp32.txt timeout 1200 python bench.py --full --steps 20 --warmup 5 > $OUT/r06_bench.json 2> $OUT/r06_bench.err
 # (6) rooflines recomputed from the kernel-trace summaries, every conv launch priced against its own pipe (--families)
 python tools/roofline_from_rocprof.py $OUT/r06_serialized_step_kernel_stats.csv 13 --families $OUT/r06_conv_table_fp32_families.json > $OUT/r06_roofline_from_rocprof.json
 python tools/roofline_from_rocprof.py $OUT/r06_train_step_kernel_stats.csv 23 --families $OUT/r06_conv_table_fp32_families.json > $OUT/r06_roofline_from_rocprof_plain_steps.json
 # (7) the RCCL code path on one rank (forced collectives): the line carries dp_exchange = per-bucket ready / start / end of the last timed step
-timeout 900 python bench.py --gpus 1 --steps 40 --warmup 10 --force-collectives --no-cpu-baseline --latency-reps 20 > $OUT/r06_bench_forced_collectives.json 2> $OUT/r06_bench_forced.err
-timeout 900 python bench.py --gpus 1 --steps 40 --warmup 10 --no-cpu-baseline --latency-reps 20 > $OUT/r06_bench_plain_40steps.json 2>> $OUT/r06_bench_forced.err
+timeout 900 python bench.py --full --gpus 1 --steps 40 --warmup 10 --force-collectives --no-cpu-baseline --latency-reps 20 > $OUT/r06_bench_forced_collectives.json 2> $OUT/r06_bench_forced.err
+timeout 900 python bench.py --full --gpus 1 --steps 40 --warmup 10 --no-cpu-baseline --latency-reps 20 > $OUT/r06_bench_plain_40steps.json 2>> $OUT/r06_bench_forced.err
 # (8) SQ wave-cycle / MFMA-busy breakdown of the conv kernels on the layer-3 problems (one PMC pass)
 bash /root/repo/tools/pmc_conv_sq.sh > $OUT/r06_conv_sq_mfma_busy.txt 2>&1
 tail -2 $OUT/r06_serial.log; grep "ms/step" $OUT/r06_plain.log; head -c 400 $OUT/r06_roofline_from_rocprof.json; tail -c 300 $OUT/r06_bench.json

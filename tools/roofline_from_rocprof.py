@@ -7,7 +7,7 @@
 belongs to one family -- x3 (conv_x3.hip: igemm_x3 / igemm_x3p / wgrad_x3), bf16 (igemm_pipe_kernel with its B16 template flag,
 wgrad_pipe16, the BF16 instantiations of the vec kernels), vector (thin-channel / 16-channel / generic kernels: no matrix core),
 f32 (everything else of the conv family: v_mfma_f32_32x32x2_f32) -- its time comes from the CSV, its algorithmic flops from the
-JSON bench.py writes next to DPFT_CONV_TABLE (dpft_profile_get_family tags of the launches).  Output adds by_family,
+JSON bench.py --full writes next to DPFT_CONV_TABLE (dpft_profile_get_family tags of the launches).  Output adds by_family,
 split_share_of_conv_flops and frac_blended = sum_i(flops_i / peak_i) / conv time (peaks 157.3 | 416.7 | 2500 | 157.3 TF).
 
     python tools/roofline_from_rocprof.py --decoder <decoder_kernel_stats.csv> [iterations_per_forward] [algorithmic_MB]

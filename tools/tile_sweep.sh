@@ -4,7 +4,7 @@
 # usage: bash tools/tile_sweep.sh [igemm|wgrad]   -> gpurun_out/tile_sweep/{igemm,wgrad}_best.txt
 mkdir -p /root/repo/gpurun_out/tile_sweep; cd /root/repo
 what=${1:-igemm}
-B="python bench.py --steps 2 --warmup 3 --no-cpu-baseline --latency-reps 3 $BENCH_ARGS"      # e.g. BENCH_ARGS="--dtype bf16 --batch 8"
+B="python bench.py --full --steps 2 --warmup 3 --no-cpu-baseline --latency-reps 3 $BENCH_ARGS"      # e.g. BENCH_ARGS="--dtype bf16 --batch 8"
 DPFT_CONV_TABLE=gpurun_out/tile_sweep/${what}_default.txt timeout 200 $B > /dev/null 2>&1
 if [ $what = igemm ]; then
   for t in 128,128 128,64 64,64; do for s in ${SPLITS:-1 2 3 4 6 8}; do
