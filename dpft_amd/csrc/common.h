@@ -78,27 +78,15 @@ __device__ __forceinline__ void fill_pro_table(float* tab, const float* bnp, con
         for (int i = tid; i < 3 * K; i += nt) tab[i] = bnp[i];
     }
 }
-// Train-mode BatchNorm finalize folded into the producing forward conv: tiles add pivoted sums to `acc` [2][K] (zero
-// before the launch, like `ticket`), the workgroup with the last ticket writes the BN block `bnp` [4][K] and updates the
-// running statistics.  `applied` (out) as in BnReduceFuse.
-struct BnFinalFuse {
-    float* acc;
-    int* ticket;
-    const float* gamma;
-    const float* beta;
-    float* running_mean;
-    float* running_var;
-    float* bnp;
-    float eps, momentum;
-    bool applied;
-    int slab = 0;      // > 0: deterministic form for launches of at most `slab` row tiles (statistics slab + per-column-tile tickets)
-    unsigned long long* sums = nullptr;      // the "sums" form (BnSumsRef): [4][K] words, zero before the launch; no ticket, nothing finalized here
-};
+// Forward conv (dpft_conv2d_nhwc_fwd_f32) with the train-mode statistics optionally as column sums.
+// `sums` (may be null; needs `stats`): [4][K] words, zero before the launch -- *sums_used tells whether the launch added to them
+// (otherwise `stats` holds the per-tile table as usual).
 // `pro_sums` (may be null): the prologue's BatchNorm comes as column sums; *pro_sums_used tells whether the kernel taken derives
 // its table from them (otherwise NOTHING was launched: the caller finalizes the layer into `pro_bn` and calls again without)
-int conv_fwd_bnfinal(const dpft_conv_desc* d, const float* x, const float* w, const float* bias, const float* pro_bn,
-                     int32_t pro_relu, float* y, float* stats, void* workspace, dpft_stream_t stream, BnFinalFuse* fuse,
-                     const BnSumsRef* pro_sums = nullptr, bool* pro_sums_used = nullptr);
+int conv_fwd_sums(const dpft_conv_desc* d, const float* x, const float* w, const float* bias, const float* pro_bn,
+                  int32_t pro_relu, float* y, float* stats, void* workspace, dpft_stream_t stream,
+                  unsigned long long* sums = nullptr, bool* sums_used = nullptr,
+                  const BnSumsRef* pro_sums = nullptr, bool* pro_sums_used = nullptr);
 int conv_dgrad_fused(const dpft_conv_desc* d, const float* dy, const float* w_t, float* dx, int32_t accumulate,
                      void* workspace, dpft_stream_t stream, BnReduceFuse* fuse);
 // bn.hip -- `act16`: the activation / gradient tensors (y, dout, out, dy, res) are bf16 in memory (the pointers keep
@@ -114,11 +102,10 @@ int bn_bwd_apply_zeroing(const float* y, const float* dout, const float* out, co
                          const unsigned char* mask8 = nullptr, bool frozen = false);      // frozen: running-statistics BN (no mean terms)
 int bn_act_any(const float* y, const float* bnp, const float* res, const float* res_bnp, int32_t relu, float* out,
                float* out32, int64_t M, int32_t K, bool act16, dpft_stream_t stream, unsigned char* mask8 = nullptr);
-// the same pass with one or both BatchNorms given as column sums (ys / rs: .sums null = take the BN block); *used = false (and
-// nothing launched) where only the generic kernel fits the shape
+// the same pass (fp32 tensors) with one or both BatchNorms given as column sums (ys / rs: .sums null = take the BN block);
+// *used = false (and nothing launched) where only the generic kernel fits the shape
 int bn_act_sums(const float* y, const float* bnp, const BnSumsRef& ys, const float* res, const float* res_bnp, const BnSumsRef& rs,
-                int32_t relu, float* out, int64_t M, int32_t K, dpft_stream_t stream, unsigned char* mask8, bool* used,
-                bool act16 = false, float* out32 = nullptr);
+                int32_t relu, float* out, int64_t M, int32_t K, dpft_stream_t stream, unsigned char* mask8, bool* used);
 struct BnSumsBatch {      // sums -> BN block [4][K] + running statistics of up to MAX layers in one launch (bn.hip)
     static constexpr int MAX = 48;      // (kernel arguments: 68 bytes per layer)
     const unsigned long long* sums[MAX];

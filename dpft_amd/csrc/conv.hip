@@ -1502,28 +1502,6 @@ static int launch_igemm(IgemmArgs& a, const TileChoice& t, bool pro, hipStream_t
     }
     // bf16 activations AND bf16 weights (act16 = 2): both operands go to the matrix cores untouched -- the pipelined kernel
     // with 2-byte elements, everything by LDS-DMA
-    if (t.vec && a.w16 && a.x16 && pro && !DGRAD && a.pro_relu && !nonlin) {
-        // bf16 operands WITH the producer's BatchNorm + ReLU (round 6): the A operand on the register route, its parameters from an
-        // LDS table; weights by LDS-DMA.  Tiles as the prologue-free form (a 256-row choice falls back to 128 x 128).
-        g_prof_family = kFamBf16;
-        if constexpr (!DGRAD) {
-            const int pbm = t.bm == 64 ? 64 : 128, pbn = (t.bm == 64 || t.bn == 64) ? 64 : 128;
-            a.mtiles = cdiv(a.M, pbm); a.ntiles = cdiv(a.N, pbn);
-            const dim3 pgrid(a.mtiles * a.ntiles * a.splits);
-            auto gop = [&](auto kernel, int pbk, size_t lds) {
-                a.ksteps = a.ksteps * BKV / pbk;
-                a.ksteps_per_split = cdiv(a.ksteps, a.splits);
-                launch_lds(kernel, pgrid, block, lds + (size_t)12 * a.C, st, a);
-            };
-#define PIPE16P_LDS(BM_, BN_, PBK_) std::max((size_t)2 * (BM_ + BN_) * PBK_ * 2, (size_t)BM_ * (BN_ + 4) * 4 + (size_t)3 * BN_ * 4)
-            if (pbm == 128 && pbn == 128) gop(igemm_pipe_kernel<128, 128, 2, 2, 64, false, true, true>, 64, PIPE16P_LDS(128, 128, 64));
-            else if (pbm == 128) gop(igemm_pipe_kernel<128, 64, 2, 2, 64, false, true, true>, 64, PIPE16P_LDS(128, 64, 64));
-            else if (a.C % 128 == 0) gop(igemm_pipe_kernel<64, 64, 2, 2, 128, false, true, true>, 128, PIPE16P_LDS(64, 64, 128));
-            else gop(igemm_pipe_kernel<64, 64, 2, 2, 64, false, true, true>, 64, PIPE16P_LDS(64, 64, 64));
-#undef PIPE16P_LDS
-        }
-        return check_launch("conv igemm (pipelined, bf16 operands, BatchNorm + ReLU prologue)");
-    }
     if (t.vec && a.w16 && a.x16 && !pro && !nonlin) {
         g_prof_family = kFamBf16;
         if (t.bm == 256) return launch_igemm_b16w(a, t.bm, t.bn, DGRAD, st);      // conv_b16w.hip: 256-row tiles, eight waves
@@ -1809,24 +1787,23 @@ extern "C" int32_t dpft_conv_get_split() { return dpft::g_conv_split; }
 
 int dpft::conv_mode_key() { return dpft::g_conv_bf16 * 2 + (dpft::g_conv_split ? 1 : 0); }
 
-extern "C" int32_t dpft_conv2d_stats_tiles(const dpft_conv_desc* d, int32_t* tile_rows) {
-    return dpft_conv2d_stats_tiles_pro(d, 0, tile_rows);
+// The forward conv goes to the streaming 1x1 kernel (conv_stream.hip): the statistics tiling and every forward entry ask this
+static bool takes_stream1x1(const dpft_conv_desc* d, int* tile_rows = nullptr) {
+    return g_conv_bf16 != 1 && stream1x1_match(d, tile_rows);
 }
 
-// `pro`: the launch will carry a BatchNorm + ReLU operand prologue (bf16 operands: the 256-row tiles have none)
-extern "C" int32_t dpft_conv2d_stats_tiles_pro(const dpft_conv_desc* d, int32_t pro, int32_t* tile_rows) {
+extern "C" int32_t dpft_conv2d_stats_tiles(const dpft_conv_desc* d, int32_t* tile_rows) {
     if (check_desc(d) != DPFT_OK) return -1;
     IgemmArgs a; fill_igemm(a, d, false);
     {
         int tr = 0;
-        if (g_conv_bf16 != 1 && stream1x1_match(d, &tr)) {      // conv_stream.hip: tile = the rows of one workgroup
+        if (takes_stream1x1(d, &tr)) {      // tile = the rows of one workgroup
             if (tile_rows) *tile_rows = tr;
             return cdiv(a.M, tr);
         }
     }
-    TileChoice t = choose_tile(a.M, a.N, a.C, a.ksteps, d->act16 ? 1 : taps_of(d));      // (as conv_fwd_bnfinal asks)
-    if (!pro) (void)big16_tile(d, a, false, false, t);
-    if (pro && d->act16 == 2 && t.bm != 64) t.bm = 128;      // (launch_igemm: the bf16 prologue kernels' tiles)
+    TileChoice t = choose_tile(a.M, a.N, a.C, a.ksteps, d->act16 ? 1 : taps_of(d));      // (as conv_fwd_sums asks)
+    (void)big16_tile(d, a, false, false, t);
     if (tile_rows) *tile_rows = t.bm;
     return cdiv(a.M, t.bm);
 }
@@ -1834,19 +1811,17 @@ extern "C" int32_t dpft_conv2d_stats_tiles_pro(const dpft_conv_desc* d, int32_t 
 extern "C" int dpft_conv2d_nhwc_fwd_f32(const dpft_conv_desc* d, const float* x, const float* w,
                                         const float* bias, const float* pro_bn, int32_t pro_relu,
                                         float* y, float* stats, void* workspace, dpft_stream_t stream) {
-    return dpft::conv_fwd_bnfinal(d, x, w, bias, pro_bn, pro_relu, y, stats, workspace, stream, nullptr);
+    return dpft::conv_fwd_sums(d, x, w, bias, pro_bn, pro_relu, y, stats, workspace, stream);
 }
 
-// Forward conv with the train-mode BatchNorm finalize folded into its epilogue (BnFinalFuse, common.h).  `fuse->applied`
-// tells whether the launch carried it (not on split-K / thin-channel / bf16-storage paths: the caller then runs
-// dpft_bn_finalize_f32 on `stats` as before).
-int dpft::conv_fwd_bnfinal(const dpft_conv_desc* d, const float* x, const float* w, const float* bias, const float* pro_bn,
-                           int32_t pro_relu, float* y, float* stats, void* workspace, dpft_stream_t stream,
-                           BnFinalFuse* fuse, const BnSumsRef* pro_sums, bool* pro_sums_used) {
-    if (fuse) fuse->applied = false;
+int dpft::conv_fwd_sums(const dpft_conv_desc* d, const float* x, const float* w, const float* bias, const float* pro_bn,
+                        int32_t pro_relu, float* y, float* stats, void* workspace, dpft_stream_t stream,
+                        unsigned long long* sums, bool* sums_used, const BnSumsRef* pro_sums, bool* pro_sums_used) {
+    if (sums_used) *sums_used = false;
     if (pro_sums_used) *pro_sums_used = false;
     if (pro_sums && !pro_sums->sums) pro_sums = nullptr;
     DPFT_REQUIRE(!pro_sums || (pro_bn && pro_sums_used), "conv fwd: a prologue from column sums needs the BN block's address and the answer slot");
+    DPFT_REQUIRE(!sums || (stats && sums_used), "conv fwd: column sums need the statistics table and the answer slot");
     int rc = check_desc(d);
     if (rc) return rc;
     DPFT_REQUIRE(x && w && y, "conv fwd: null tensor");
@@ -1859,12 +1834,18 @@ int dpft::conv_fwd_bnfinal(const dpft_conv_desc* d, const float* x, const float*
     if (conv16_matches(d) && !pro_bn && !stats) return conv16_forward(d, x, w, bias, y, st);
     static const bool thin_fwd = getenv("DPFT_THIN_FWD") == nullptr || atoi(getenv("DPFT_THIN_FWD")) != 0;      // A/B switch
     if (thin_fwd && conv1x1_to16_matches(d) && !pro_bn && !stats) return conv1x1_to16_forward(d, x, w, bias, y, st);
-    if (g_conv_bf16 != 1 && !bias && (!pro_bn || pro_relu) && !(fuse && fuse->acc) && stream1x1_match(d, nullptr)) {
-        g_prof_family = kFamF32;      // short reduction, wide output, large map: the streaming kernel (conv_stream.hip)
-        unsigned long long* bns = fuse && fuse->sums && stats && (int64_t)d->B * d->OH * d->OW < (1 << 22) ? fuse->sums : nullptr;
-        if (bns) fuse->applied = true;
-        if (pro_sums) *pro_sums_used = true;
-        return launch_stream1x1(d, x, w, pro_bn, y, stats, nullptr, nullptr, 0, st, bns, pro_sums);
+    if (takes_stream1x1(d)) {
+        // short reduction, wide output, large map: the streaming kernel (conv_stream.hip), which has no bias and only the
+        // BatchNorm + ReLU prologue.  Statistics must come in its tiling (dpft_conv2d_stats_tiles): no other kernel may take them.
+        const bool fits = !bias && (!pro_bn || pro_relu);
+        DPFT_REQUIRE(fits || !stats, "conv fwd: statistics of a streaming 1x1 conv (%d -> %d) take no bias and only the BatchNorm + ReLU prologue", d->C, d->K);
+        if (fits) {
+            g_prof_family = kFamF32;
+            unsigned long long* bns = sums && (int64_t)d->B * d->OH * d->OW < (1 << 22) ? sums : nullptr;
+            if (bns) *sums_used = true;
+            if (pro_sums) *pro_sums_used = true;
+            return launch_stream1x1(d, x, w, pro_bn, y, stats, nullptr, nullptr, 0, st, bns, pro_sums);
+        }
     }
     IgemmArgs a; fill_igemm(a, d, false);
     a.x = x; a.w = w; a.y = y; a.bias = bias; a.stats = stats;
@@ -1872,7 +1853,7 @@ int dpft::conv_fwd_bnfinal(const dpft_conv_desc* d, const float* x, const float*
     a.x16 = a.y16 = d->act16 != 0;
     a.w16 = d->act16 == 2;
     if (d->a_planes && d->w_planes && !pro_bn && !d->act16) { a.x3 = d->a_planes; a.w3 = d->w_planes; }
-    DPFT_REQUIRE(!(a.w16 && (bias || (pro_bn && !pro_relu))), "conv fwd: act16 = 2 (bf16 weights) takes no bias and only the BatchNorm + ReLU prologue");
+    DPFT_REQUIRE(!(a.w16 && (bias || pro_bn)), "conv fwd: act16 = 2 (bf16 weights) takes no bias and no operand prologue");
     const bool pro = pro_bn != nullptr;
     TileChoice t = choose_tile(a.M, a.N, a.C, a.ksteps, (d->act16 || (pro && !pro_relu)) ? 1 : taps_of(d));
     const bool big16 = !pro && !bias && big16_tile(d, a, false, workspace != nullptr, t);
@@ -1893,26 +1874,12 @@ int dpft::conv_fwd_bnfinal(const dpft_conv_desc* d, const float* x, const float*
         fixup = sk_fixup_ok(a, t.splits, 1);
         if (fixup) a.sk_ticket = reinterpret_cast<int*>(workspace);      // the last split workgroup of a tile runs the whole epilogue
         else a.stats = nullptr;
-    } else if (fuse && fuse->acc && fuse->slab && stats && !bias && !d->act16 && t.vec && (a.N & 3) == 0 &&
-               cdiv(a.M, t.bm) <= fuse->slab) {
-        // deterministic form: the slab stays, one ticket per column tile (the zeroed accumulator region holds them: 2 K >= tiles)
-        a.bnf_slab = 1; a.bnf_ticket = reinterpret_cast<int*>(fuse->acc); a.bnf_gamma = fuse->gamma; a.bnf_beta = fuse->beta;
-        a.bnf_rm = fuse->running_mean; a.bnf_rv = fuse->running_var; a.bnf_bnp = fuse->bnp;
-        a.bnf_eps = fuse->eps; a.bnf_mom = fuse->momentum;
-        fuse->applied = true;
-    } else if (fuse && fuse->acc && !fuse->slab && !bias && !d->act16 && t.vec && (a.N & 3) == 0) {
-        a.bnf_acc = fuse->acc; a.bnf_ticket = fuse->ticket; a.bnf_gamma = fuse->gamma; a.bnf_beta = fuse->beta;
-        a.bnf_rm = fuse->running_mean; a.bnf_rv = fuse->running_var; a.bnf_bnp = fuse->bnp;
-        a.bnf_eps = fuse->eps; a.bnf_mom = fuse->momentum;
-        a.stats = nullptr;
-        fuse->applied = true;
     }
     // (the accumulators' low words hold 65 536 addends: tiles of >= 64 rows)
-    if (fuse && fuse->sums && !fuse->applied && stats && !bias && t.vec && (a.N & 3) == 0 && (t.splits == 1 || fixup) &&
-        a.M < (1 << 22)) {
-        a.bns = fuse->sums;      // column sums instead of the per-tile table; finalized by nobody here
+    if (sums && !bias && t.vec && (a.N & 3) == 0 && (t.splits == 1 || fixup) && a.M < (1 << 22)) {
+        a.bns = sums;      // column sums instead of the per-tile table; finalized by nobody here
         a.stats = nullptr;
-        fuse->applied = true;
+        *sums_used = true;
     }
     rc = launch_igemm<false>(a, t, pro, st);
     if (rc) return rc;
@@ -1943,7 +1910,7 @@ extern "C" int dpft_conv2d_nhwc_fwd_bnact_f32(const dpft_conv_desc* d, const flo
     if (rc) return rc;
     DPFT_REQUIRE(x && w && y && out_bn, "conv fwd_bnact: null tensor");
     hipStream_t st = (hipStream_t)stream;
-    if (g_conv_bf16 != 1 && stream1x1_match(d, nullptr)) {      // conv_stream.hip
+    if (takes_stream1x1(d)) {
         ProfScope prof(0, d, st);
         g_prof_family = kFamF32;
         return launch_stream1x1(d, x, w, nullptr, y, nullptr, out_bn, residual, relu, st);

@@ -260,7 +260,7 @@ static size_t b16w_lds() {
 // `a` prepared as for igemm_pipe_kernel<BM, BN, ..> (mtiles, ntiles, splits, ksteps in units of 64, ksteps_per_split)
 int launch_igemm_b16w(IgemmArgs& a, int bm, int bn, bool dgrad, hipStream_t st) {
     DPFT_REQUIRE(a.x16 && a.w16 && a.pro == nullptr, "conv (bf16, large tiles): bf16 operands without prologue only");
-    DPFT_REQUIRE(a.bnf_acc == nullptr && a.bnf_slab == 0, "conv (bf16, large tiles): no fused BatchNorm finalize");
+    DPFT_REQUIRE(a.bns == nullptr, "conv (bf16, large tiles): statistics as per-tile tables only");
     DPFT_REQUIRE((a.N & 3) == 0 && a.C % 64 == 0, "conv (bf16, large tiles): N %% 4 == 0 and C %% 64 == 0");
     DPFT_REQUIRE(bm == 256 && (bn == 256 || bn == 128), "conv (bf16, large tiles): tile %d x %d", bm, bn);
     const dim3 grid(a.mtiles * a.ntiles * a.splits), block(512);

@@ -110,20 +110,6 @@ struct IgemmArgs {
     const unsigned char* bnr_mask8;    // ReLU byte mask of the layer's OUTPUT side (1 byte per 4 channels), or null
     int bnr_self_mask;                 // mask = bn(y) > 0 (the ReLU sits directly behind this BatchNorm)
     float* bnr_sums;                   // null = no fused reduction
-    // Fused BatchNorm FINALIZE of a train-mode forward conv (dpft::BnFinalFuse): instead of writing its (mean, M2) pair to
-    // the per-tile statistics table, a tile adds n (mean - p) and M2 + n (mean - p)^2 to two accumulators per channel
-    // (p = running mean: the pivot of bn_finalize_kernel's merge, same algebra); the workgroup that draws the last
-    // ticket turns them into the BN block and updates the running statistics -- no bn_finalize launch between the conv
-    // and its consumer.
-    float* bnf_acc;                    // [2][N], zero before the launch; null = off
-    int* bnf_ticket;                   // zero before the launch
-    int bnf_slab;                      // deterministic form: per-tile statistics slab + one ticket per column tile (below)
-    const float* bnf_gamma;
-    const float* bnf_beta;
-    float* bnf_rm;                     // running mean / var (may be null)
-    float* bnf_rv;
-    float* bnf_bnp;                    // out: BN block [4][N]
-    float bnf_eps, bnf_mom;
 };
 
 // output row (GEMM row m) -> pixel index of the output tensor
@@ -274,7 +260,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x16 (&acc)
         __syncthreads();      // the statistics / staging below reuse the same LDS
     }
     const bool part = !HAS_PF && a.partial != nullptr && !fix;      // this launch leaves partial tiles for a reduction kernel
-    if (!HAS_PF && (a.stats != nullptr || a.bnf_acc != nullptr || a.bns != nullptr)) {
+    if (!HAS_PF && (a.stats != nullptr || a.bns != nullptr)) {
         // ---- per-tile column statistics of the raw conv output (bias-free by construction) ----
         float* red = smem;               // [WGM][BN]
         float* smean = smem + WGM * BN;  // [BN]
@@ -299,11 +285,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x16 (&acc)
             for (int i = 0; i < WGM; ++i) s += red[i * BN + tid];
             const float mean = s / (float)cnt;
             smean[tid] = mean;
-            if (a.stats && n0 + tid < a.N) {
-                float* dst = a.stats + ((size_t)mt * 2 + 0) * a.N + n0 + tid;
-                if (a.bnf_slab) __hip_atomic_store(dst, mean, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // read by ANOTHER workgroup of this launch
-                else *dst = mean;
-            }
+            if (a.stats && n0 + tid < a.N) a.stats[((size_t)mt * 2 + 0) * a.N + n0 + tid] = mean;
         }
         __syncthreads();
 #pragma unroll
@@ -326,21 +308,10 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x16 (&acc)
             float s = 0.f;
 #pragma unroll
             for (int i = 0; i < WGM; ++i) s += red[i * BN + tid];
-            if (a.stats) {
-                float* dst = a.stats + ((size_t)mt * 2 + 1) * a.N + n0 + tid;
-                if (a.bnf_slab) __hip_atomic_store(dst, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else *dst = s;
-            }
+            if (a.stats) a.stats[((size_t)mt * 2 + 1) * a.N + n0 + tid] = s;
             if (a.bns) {      // "sums" form: n * mean and M2 + n * mean^2 (fp64: exact products) into the fixed-point accumulators
                 const double m = (double)smean[tid], fc = (double)cnt;
                 bn_sums_add(a.bns, a.N, n0 + tid, fc * m, (double)s + fc * m * m);
-            }
-            if (a.bnf_acc) {      // fused finalize: this tile's share of the pivoted sums (device-scope atomics)
-                const int n = n0 + tid;
-                const float dlt = smean[tid] - (a.bnf_rm ? a.bnf_rm[n] : 0.f);
-                const float fc = (float)cnt;
-                atomicAdd(a.bnf_acc + n, fc * dlt);
-                atomicAdd(a.bnf_acc + a.N + n, fmaf(fc * dlt, dlt, s));
             }
         }
         __syncthreads();
@@ -531,111 +502,6 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x16 (&acc)
             }
         }
     }
-    if (!HAS_PF && a.bnf_slab) {
-        // Deterministic BatchNorm finalize inside the forward conv: the workgroups of one COLUMN tile take tickets; whoever
-        // draws the last one merges that tile's columns of the statistics slab with the arithmetic of bn_finalize_kernel
-        // (bn.hip: 32 tile groups per channel, pivot = tile 0, groups summed in order) -- bit-identical to the separate
-        // launch, whichever workgroup ends up doing it.  No fences: the slab entries were written with agent-scope stores
-        // (performed at the coherence point once vmcnt acknowledges them), the tickets are agent-scope RMWs, the merger reads
-        // the slab with agent-scope loads; its plain stores of the BN block are consumed by LATER kernels.
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        int* flag = reinterpret_cast<int*>(smem);
-        if (tid == 0) *flag = __hip_atomic_fetch_add(a.bnf_ticket + n0 / BN, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        if (*flag == a.mtiles - 1) {
-            constexpr int R = NT / BN;      // threads per channel
-            float* s1s = smem + 64;         // [32][BN]
-            float* s2s = s1s + 32 * BN;
-            const int cl = tid % BN, r = tid / BN, c = n0 + cl;
-            const bool ok = c < a.N;
-            auto ld = [&](size_t i) { return __hip_atomic_load(a.stats + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-            const float pivot = ok ? ld(c) : 0.f;
-            const float full = (float)BM;
-            const float last = (float)((int64_t)a.M - (int64_t)(a.mtiles - 1) * BM);
-            // all of this thread's slab entries are requested before the first is used (atomic loads are not hoisted or
-            // pipelined by the compiler: one at a time they cost 57 memory round trips, ~14 us at the end of the conv)
-            constexpr int GP = 32 / R, TPG = 2;      // groups per thread, tiles per group (launches of <= 64 row tiles)
-            float mv[GP][TPG], qv[GP][TPG];
-#pragma unroll
-            for (int gi = 0; gi < GP; ++gi)
-#pragma unroll
-                for (int ti = 0; ti < TPG; ++ti) {
-                    const int t = r + gi * R + ti * 32;
-                    const bool on = ok && t < a.mtiles;
-                    mv[gi][ti] = on ? ld(((size_t)t * 2 + 0) * a.N + c) : 0.f;
-                    qv[gi][ti] = on ? ld(((size_t)t * 2 + 1) * a.N + c) : 0.f;
-                }
-#pragma unroll
-            for (int gi = 0; gi < GP; ++gi) {
-                float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-                for (int ti = 0; ti < TPG; ++ti) {
-                    const int t = r + gi * R + ti * 32;
-                    if (ok && t < a.mtiles) {
-                        const float cnt = t == a.mtiles - 1 ? last : full;
-                        const float d = mv[gi][ti] - pivot;
-                        s1 = fmaf(cnt, d, s1);
-                        s2 += fmaf(cnt * d, d, qv[gi][ti]);
-                    }
-                }
-                s1s[(r + gi * R) * BN + cl] = s1;
-                s2s[(r + gi * R) * BN + cl] = s2;
-            }
-            __syncthreads();
-            if (tid < BN && ok) {
-                float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-                for (int i = 0; i < 32; ++i) { s1 += s1s[i * BN + cl]; s2 += s2s[i * BN + cl]; }
-                const float invN = 1.0f / (float)a.M;
-                const float mean = fmaf(s1, invN, pivot);
-                const float m2 = fmaxf(s2 - s1 * s1 * invN, 0.f);
-                const float var = m2 * invN;
-                const float invstd = 1.0f / sqrtf(var + a.bnf_eps);
-                a.bnf_bnp[c] = mean;
-                a.bnf_bnp[a.N + c] = a.bnf_gamma[c] * invstd;
-                a.bnf_bnp[2 * a.N + c] = a.bnf_beta[c];
-                a.bnf_bnp[3 * a.N + c] = invstd;
-                if (a.bnf_rm) {
-                    const float unbiased = a.M > 1 ? m2 / (float)(a.M - 1) : var;
-                    a.bnf_rm[c] = (1.f - a.bnf_mom) * a.bnf_rm[c] + a.bnf_mom * mean;
-                    a.bnf_rv[c] = (1.f - a.bnf_mom) * a.bnf_rv[c] + a.bnf_mom * unbiased;
-                }
-            }
-        }
-    }
-    if (!HAS_PF && a.bnf_acc != nullptr) {
-        // Every tile has added its sums with device-scope atomics; an atomic is acknowledged (vmcnt) once it has been
-        // performed at the coherence point, so "wait for mine, then take a ticket" orders them before the last ticket --
-        // no release fence (nothing here publishes plain stores), the last workgroup reads the totals with device-scope
-        // atomic loads.  Its plain stores of the BN block are consumed by LATER kernels.
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        int* flag = reinterpret_cast<int*>(smem);
-        if (tid == 0) *flag = __hip_atomic_fetch_add(a.bnf_ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        if (*flag == a.mtiles * a.ntiles - 1) {
-            const float invN = 1.0f / (float)a.M;
-            for (int c = tid; c < a.N; c += NT) {
-                const float s1 = __hip_atomic_load(a.bnf_acc + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const float s2 = __hip_atomic_load(a.bnf_acc + a.N + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const float pivot = a.bnf_rm ? a.bnf_rm[c] : 0.f;
-                const float mean = fmaf(s1, invN, pivot);
-                const float m2 = fmaxf(s2 - s1 * s1 * invN, 0.f);
-                const float var = m2 * invN;
-                const float invstd = 1.0f / sqrtf(var + a.bnf_eps);
-                a.bnf_bnp[c] = mean;
-                a.bnf_bnp[a.N + c] = a.bnf_gamma[c] * invstd;
-                a.bnf_bnp[2 * a.N + c] = a.bnf_beta[c];
-                a.bnf_bnp[3 * a.N + c] = invstd;
-                if (a.bnf_rm) {
-                    const float unbiased = a.M > 1 ? m2 / (float)(a.M - 1) : var;
-                    a.bnf_rm[c] = (1.f - a.bnf_mom) * pivot + a.bnf_mom * mean;
-                    a.bnf_rv[c] = (1.f - a.bnf_mom) * a.bnf_rv[c] + a.bnf_mom * unbiased;
-                }
-            }
-        }
-    }
 }
 
 __device__ __forceinline__ void decode_tile(const IgemmArgs& a, int& mt, int& nt, int& split) {
@@ -676,8 +542,6 @@ struct WgradArgs {
 
 // conv_x3.hip: the 3 x bf16 split main loop (fp32 results from the bf16 matrix cores); `a` prepared as for igemm_pipe_kernel
 int launch_igemm_x3(IgemmArgs& a, int bm, int bn, bool dgrad, bool pro, hipStream_t st);
-// conv_x3w.hip: the same arithmetic on eight waves per 128 x 128 tile (`a` as launch_igemm_x3 prepared it)
-int launch_igemm_x3w(IgemmArgs& a, bool dgrad, bool pro, hipStream_t st);
 int split_planes(const float* src, void* dst, int64_t n, hipStream_t st);
 // conv_stream.hip: 1x1 convs with 64 / 128 input channels and K % 256 == 0 on large maps (weights in LDS, rows private to a wave)
 bool stream1x1_match(const dpft_conv_desc* d, int* tile_rows);

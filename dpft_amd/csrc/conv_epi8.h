@@ -1,7 +1,8 @@
-// Epilogue of the eight-wave implicit-GEMM kernels (conv_b16w.hip, conv_x3w.hip): the tile leaves the accumulators in 64-row
-// (BM / 4) chunks through one staging buffer -- or, for bf16 outputs without an additive operand, packed as bf16 by all waves
-// at once -- and carries every form of conv_core.h's igemm_epilogue: split-K fix-up (ticket per output tile), BatchNorm tile
-// statistics, bias, residual + ReLU byte mask, accumulate, the fused BatchNorm-backward reduction, the inference BN / add / ReLU form.
+// Epilogue of the eight-wave implicit-GEMM kernel (conv_b16w.hip): the tile leaves the accumulators in 64-row (BM / 4) chunks
+// through one staging buffer -- or, for bf16 outputs without an additive operand, packed as bf16 by all waves at once -- and
+// carries the forms of conv_core.h's igemm_epilogue: split-K fix-up (ticket per output tile), BatchNorm tile statistics (the
+// per-tile table; no column sums), bias, residual + ReLU byte mask, accumulate, the fused BatchNorm-backward reduction, the
+// inference BN / add / ReLU form.
 #pragma once
 #include "conv_core.h"
 
@@ -114,7 +115,7 @@ __device__ __forceinline__ void epilogue_w8(const IgemmArgs& a, f32x16 (&acc)[RB
     }
     const bool part = a.partial != nullptr && !fix;      // partial tiles for a reduction kernel of the caller
     // ---- per-tile column statistics of the raw conv output: (mean, M2) of the tile's rows ----
-    if ((a.stats != nullptr || a.bns != nullptr) && !(a.ablate & 32)) {
+    if (a.stats != nullptr && !(a.ablate & 32)) {
         float* red = smem;               // [WGM][BN]
         float* smean = smem + WGM * BN;  // [BN]
         const int cnt = min(BM, a.M - m0);
@@ -139,7 +140,7 @@ __device__ __forceinline__ void epilogue_w8(const IgemmArgs& a, f32x16 (&acc)[RB
             for (int i = 0; i < WGM; ++i) s += red[i * BN + tid];
             const float mean = s / (float)cnt;
             smean[tid] = mean;
-            if (a.stats && n0 + tid < a.N) a.stats[((size_t)mt * 2 + 0) * a.N + n0 + tid] = mean;
+            if (n0 + tid < a.N) a.stats[((size_t)mt * 2 + 0) * a.N + n0 + tid] = mean;
         }
         __syncthreads();
 #pragma unroll
@@ -162,11 +163,7 @@ __device__ __forceinline__ void epilogue_w8(const IgemmArgs& a, f32x16 (&acc)[RB
             float s = 0.f;
 #pragma unroll
             for (int i = 0; i < WGM; ++i) s += red[i * BN + tid];
-            if (a.stats) a.stats[((size_t)mt * 2 + 1) * a.N + n0 + tid] = s;
-            if (a.bns) {      // the statistics as column sums (common.h: BnSumsRef)
-                const double m = (double)smean[tid], fc = (double)cnt;
-                bn_sums_add(a.bns, a.N, n0 + tid, fc * m, (double)s + fc * m * m);
-            }
+            a.stats[((size_t)mt * 2 + 1) * a.N + n0 + tid] = s;
         }
         __syncthreads();
     }

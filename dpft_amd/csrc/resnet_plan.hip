@@ -14,16 +14,6 @@
 
 namespace dpft {
 
-// bf16 plan (act16 = 2), round 6 experiment (DPFT_PRO16=1): conv2 / conv3 read the RAW bf16 outputs y1 / y2 through the BatchNorm + ReLU
-// operand prologue of the bf16 pipelined kernel (conv_pipe.h) instead of materialised a1 / a2 -- two elementwise launches per bottleneck
-// leave the forward's chain; the weight gradients, which still want the materialised operand, get it on the side stream right before
-// they run.  Measured at bf16 batch 8 (same box, two rounds): 22.75 / 22.51 ms materialising vs 22.81 / 22.70 with the prologues -- the
-// register-route GEMMs (and conv3 losing its 256-row tiles) cost what the 66 launches cost.  Off.
-static bool pro16_on() {
-    static const bool on = getenv("DPFT_PRO16") != nullptr && atoi(getenv("DPFT_PRO16")) != 0;
-    return on;
-}
-
 struct ConvRef {
     dpft_conv_desc d{};
     int w;  // index into the conv table
@@ -65,7 +55,7 @@ struct ResnetPlan {
     size_t g_off[2];
     size_t gmax;            // floats of the largest activation gradient
     size_t o_dy, o_da, o_dd, o_wt, o_sums;   // backward scratch offsets (floats)
-    std::vector<size_t> bnacc;      // per BatchNorm: float offset of its fused-finalize accumulators [2][K] + ticket (16 floats)
+    std::vector<size_t> bnacc;      // per BatchNorm: float offset of its column-sum accumulators ([4][K] 64-bit words, common.h: BnSumsRef)
     size_t o_bnacc = 0, bnacc_floats = 0;
     // "sums" form of the train-mode statistics (common.h: BnSumsRef): layers whose BN block has not been written yet in THIS forward
     // (their consumers derive the parameters from the column sums; the batched finalize at the end of the forward writes the blocks)
@@ -148,9 +138,9 @@ extern "C" int64_t dpft_resnet_plan_create(const dpft_resnet_desc* desc) {
     };
     size_t gmax = 0;
     auto track_g = [&](size_t n) { if (n > gmax) gmax = n; };
-    auto stats_of = [&](const dpft_conv_desc& d, int& tiles, int& rows, bool pro = false) {
+    auto stats_of = [&](const dpft_conv_desc& d, int& tiles, int& rows) {
         int32_t r = 0;
-        tiles = dpft_conv2d_stats_tiles_pro(&d, pro ? 1 : 0, &r);
+        tiles = dpft_conv2d_stats_tiles(&d, &r);
         rows = r;
         return (size_t)tiles * 2 * d.K;
     };
@@ -210,8 +200,8 @@ extern "C" int64_t dpft_resnet_plan_create(const dpft_resnet_desc* desc) {
                 if (bp.has_ds) bp.cd.w16 = take((nelem_w(bp.cd.d) + 1) / 2);
             }
             bp.y1 = take(nelem_out(bp.c1.d));  bp.p1 = take(4 * planes);  bp.s1 = take(stats_of(bp.c1.d, bp.t1, bp.r1));
-            bp.y2 = take(nelem_out(bp.c2.d));  bp.p2 = take(4 * planes);  bp.s2 = take(stats_of(bp.c2.d, bp.t2, bp.r2, desc->act16 == 2 && pro16_on()));
-            bp.y3 = take(nelem_out(bp.c3.d));  bp.p3 = take(4 * planes * 4);  bp.s3 = take(stats_of(bp.c3.d, bp.t3, bp.r3, desc->act16 == 2 && pro16_on()));
+            bp.y2 = take(nelem_out(bp.c2.d));  bp.p2 = take(4 * planes);  bp.s2 = take(stats_of(bp.c2.d, bp.t2, bp.r2));
+            bp.y3 = take(nelem_out(bp.c3.d));  bp.p3 = take(4 * planes * 4);  bp.s3 = take(stats_of(bp.c3.d, bp.t3, bp.r3));
             if (bp.has_ds) {
                 bp.yd = take(nelem_out(bp.cd.d));  bp.pd = take(4 * planes * 4);  bp.sd = take(stats_of(bp.cd.d, bp.td, bp.rd));
                 track_ws(bp.cd.d);
@@ -232,10 +222,10 @@ extern "C" int64_t dpft_resnet_plan_create(const dpft_resnet_desc* desc) {
     }
     p->n_conv = nconv;
     p->n_bn = nbn;
-    {   // accumulators of the fused BatchNorm finalize (conv epilogue): one zero-fill per forward covers them all
+    {   // column-sum accumulators of the train-mode statistics (conv epilogues): one zero-fill per forward covers them all
         p->bnacc.assign(nbn, 0);
         size_t acc = 0;
-        auto add = [&](int bn, int K) { p->bnacc[bn] = acc; acc += align64((size_t)8 * K + 16); };      // (the sums form: [4][K] 64-bit words)
+        auto add = [&](int bn, int K) { p->bnacc[bn] = acc; acc += align64((size_t)8 * K); };      // [4][K] 64-bit words
         add(p->bn0, 64);
         for (const BlockPlan& b : p->blocks) {
             add(b.bn1, b.c1.d.K); add(b.bn2, b.c2.d.K); add(b.bn3, b.c3.d.K);
@@ -340,24 +330,13 @@ static int bn_params(const ResnetPlan* p, const Tables& T, int bn, const float* 
     return DPFT_OK;      // eval: every BN block was produced up front by eval_bn_blocks()
 }
 
-// train-mode forward conv + its BatchNorm block.  Default: per-tile statistics in the conv epilogue + bn_finalize.  The
-// finalize can ride in the conv's epilogue instead (BnFinalFuse, DPFT_BN_FINAL_FUSE):
-//   1  atomic accumulation + last-ticket workgroup: -0.4 ... -1.1 ms per step, but the forward's BatchNorm blocks then differ
-//      in the last bits from run to run, which the encoders' backward amplifies (the full-size repeatability property no
-//      longer holds to 2e-4);
-//   2  deterministic: the statistics slab stays, the workgroups of a column tile take tickets and the last one merges that
-//      tile's columns with bn_finalize_kernel's own arithmetic (bit-identical results, all parity tests green), for launches
-//      of <= 64 row tiles (camera layers 3-4: 80 of its 104 BatchNorms).  Measured: 80 launches fewer, step time unchanged
-//      (28.95 vs 29.0 ms) -- the merger's ~3 us at the end of each conv (one ticket round trip + 64 slab loads in flight; a
-//      first form with the loads one at a time cost 14 us and LOST 0.5 ms) are what the removed kernel boundary cost.
-// Both stay off: neither beats the separate 5 us kernel by enough to carry the extra memory-ordering argument.
-// The "sums" form (DPFT_BN_SUMS, fp32 tensors): no finalize launch between a conv and its consumer at all -- see common.h: BnSumsRef.
+// train-mode forward conv + its BatchNorm block: per-tile statistics in the conv epilogue + bn_finalize, or -- the "sums" form
+// (DPFT_BN_SUMS, fp32 tensors) -- no finalize launch between a conv and its consumer at all: see common.h: BnSumsRef.
 static bool bn_sums_on(const ResnetPlan* p) {
     static const int on = getenv("DPFT_BN_SUMS") ? atoi(getenv("DPFT_BN_SUMS")) : 1;      // A/B switch: 0 = per-tile tables + one bn_finalize launch per layer
-    static const int fuse_mode = getenv("DPFT_BN_FINAL_FUSE") ? atoi(getenv("DPFT_BN_FINAL_FUSE")) : 0;
-    // (bf16 operands, act16 = 2: built and measured -- DPFT_BN_SUMS=2 -- and off: there the consumers are the materialising
-    // elementwise passes, and the step does not gain: batch 8, same box, 22.57 / 22.57 ms with the tables, 22.83 / 22.71 with the sums)
-    return on != 0 && fuse_mode == 0 && (p->desc.act16 == 0 || (on == 2 && p->desc.act16 == 2)) && !p->frozen;
+    // (bf16 operands, act16 = 2: built, measured and removed -- there the consumers are the materialising elementwise passes, and the
+    // step did not gain: batch 8, same box, 22.57 / 22.57 ms with the tables, 22.83 / 22.71 with the sums)
+    return on != 0 && p->desc.act16 == 0 && !p->frozen;
 }
 static BnSumsRef bn_sums_ref(const ResnetPlan* p, const Tables& T, float* A, int bn, int K, int64_t M) {
     return BnSumsRef{(const unsigned long long*)(A + p->o_bnacc + p->bnacc[bn]), T.gamma(bn), T.beta(bn), 1.0 / (double)M, p->desc.eps, K};
@@ -406,29 +385,22 @@ static int conv_bn_train(ResnetPlan* p, const Tables& T, const ConvRef& c, int b
                          dpft_stream_t st, const float* w = nullptr, int pro_bn = -1, int pro_K = 0, int64_t pro_M = 0) {
     if (!w) w = T.w(c.w);
     if (p->frozen)      // the BN block comes from the running statistics (eval_bn_blocks): no statistics, no finalize
-        return conv_fwd_bnfinal(&c.d, x, w, nullptr, pro, pro ? 1 : 0, y, nullptr, ws, st, nullptr);
-    static const int fuse_mode = getenv("DPFT_BN_FINAL_FUSE") ? atoi(getenv("DPFT_BN_FINAL_FUSE")) : 0;      // 0 off | 1 atomics | 2 slab
-    static const int slab_tiles = getenv("DPFT_BN_FINAL_TILES") ? std::min(64, atoi(getenv("DPFT_BN_FINAL_TILES"))) : 64;      // the merger holds two tiles per group in registers
-    float* acc = A + p->o_bnacc + p->bnacc[bn];
-    BnFinalFuse f{acc, (int*)(acc + 2 * c.d.K), T.gamma(bn), T.beta(bn), T.rm(bn), T.rv(bn), bnp, p->desc.eps, p->desc.momentum, false,
-                  fuse_mode == 2 ? slab_tiles : 0};
-    const bool sums = bn_sums_on(p);
-    if (sums) { f.acc = nullptr; f.ticket = nullptr; f.sums = (unsigned long long*)acc; }
-    bool launched = false;
+        return conv_fwd_sums(&c.d, x, w, nullptr, pro, pro ? 1 : 0, y, nullptr, ws, st);
+    unsigned long long* sums = bn_sums_on(p) ? (unsigned long long*)(A + p->o_bnacc + p->bnacc[bn]) : nullptr;
+    bool sums_used = false, launched = false;
     if (sums && pro && pro_bn >= 0 && p->bn_pending[pro_bn]) {
         const BnSumsRef ps = bn_sums_ref(p, T, A, pro_bn, pro_K, pro_M);
         bool used = false;
-        RC(conv_fwd_bnfinal(&c.d, x, w, nullptr, pro, 1, y, stats, ws, st, &f, &ps, &used));
+        RC(conv_fwd_sums(&c.d, x, w, nullptr, pro, 1, y, stats, ws, st, sums, &sums_used, &ps, &used));
         launched = used;
         if (!used) RC(bn_finalize_one(p, T, A, pro_bn, st));      // this conv's kernel reads BN blocks only
     }
-    if (!launched) RC(conv_fwd_bnfinal(&c.d, x, w, nullptr, pro, pro ? 1 : 0, y, stats, ws, st, (fuse_mode || sums) ? &f : nullptr));
-    if (f.applied && f.sums) {
+    if (!launched) RC(conv_fwd_sums(&c.d, x, w, nullptr, pro, pro ? 1 : 0, y, stats, ws, st, sums, &sums_used));
+    if (sums_used) {
         p->bn_pending[bn] = 1;
         p->pend_list.push_back(ResnetPlan::PendingBn{bn, c.d.K, (long long)M, (size_t)(bnp - A)});
         return DPFT_OK;
     }
-    if (f.applied) return DPFT_OK;
     return dpft_bn_finalize_f32(stats, tiles, rows, M, c.d.K, T.gamma(bn), T.beta(bn), p->desc.eps, p->desc.momentum, T.rm(bn),
                                 T.rv(bn), bnp, st);
 }
@@ -472,7 +444,7 @@ static int train_act_pass(ResnetPlan* p, const Tables& T, float* A, const float*
         const BnSumsRef ys = py ? bn_sums_ref(p, T, A, bn, K, M) : BnSumsRef{};
         const BnSumsRef rs = pr ? bn_sums_ref(p, T, A, res_bn, K, M) : BnSumsRef{};
         bool done = false;
-        RC(bn_act_sums(y, bnp, ys, res, res_bnp, rs, 1, out, M, K, st, mask, &done, a16, out32));
+        RC(bn_act_sums(y, bnp, ys, res, res_bnp, rs, 1, out, M, K, st, mask, &done));
         if (done) return DPFT_OK;
         if (py) RC(bn_finalize_one(p, T, A, bn, st));
         if (pr) RC(bn_finalize_one(p, T, A, res_bn, st));
@@ -497,8 +469,7 @@ static int forward_impl(ResnetPlan* p, const float* x, const dpft_resnet_tables*
         RC(dpft_conv2d_nhwc_fwd_f32(&p->adj.d, x, T.w(p->adj.w), nullptr, nullptr, 0, A + p->xa, nullptr, ws, st));
         xa = A + p->xa;
     }
-    static const bool final_fuse = getenv("DPFT_BN_FINAL_FUSE") != nullptr && atoi(getenv("DPFT_BN_FINAL_FUSE")) != 0;
-    if (tr && (final_fuse || bn_sums_on(p))) RC(zero_fill(A + p->o_bnacc, p->bnacc_floats * sizeof(float), st));
+    if (tr && bn_sums_on(p)) RC(zero_fill(A + p->o_bnacc, p->bnacc_floats * sizeof(float), st));
     p->pend_list.clear();
     std::fill(p->bn_pending.begin(), p->bn_pending.end(), 0);
     RC(dpft_conv2d_nhwc_fwd_f32(&p->c0.d, xa, T.w(p->c0.w), nullptr, nullptr, 0, A + p->y0, tr && !p->frozen ? A + p->s0 : nullptr, ws, st));
@@ -561,15 +532,10 @@ static int forward_impl(ResnetPlan* p, const float* x, const dpft_resnet_tables*
             // bf16 weights: no operand prologues -- relu(bn(y)) is materialised (bf16) by one elementwise pass per layer and
             // every GEMM is the LDS-DMA kernel
             RC(conv_bn_train(p, T, b.c1, b.bn1, A + b.x, nullptr, A, A + b.y1, A + b.s1, b.t1, b.r1, M1, A + b.p1, ws, st, A + b.c1.w16));
-            if (pro16_on()) {
-                RC(conv_bn_train(p, T, b.c2, b.bn2, A + b.y1, A + b.p1, A, A + b.y2, A + b.s2, b.t2, b.r2, M2, A + b.p2, ws, st, A + b.c2.w16));
-                RC(conv_bn_train(p, T, b.c3, b.bn3, A + b.y2, A + b.p2, A, A + b.y3, A + b.s3, b.t3, b.r3, M2, A + b.p3, ws, st, A + b.c3.w16));
-            } else {
             RC(train_act_pass(p, T, A, A + b.y1, b.bn1, b.c1.d.K, M1, A + b.p1, nullptr, -1, nullptr, A + b.a1, nullptr, true, st, nullptr));
             RC(conv_bn_train(p, T, b.c2, b.bn2, A + b.a1, nullptr, A, A + b.y2, A + b.s2, b.t2, b.r2, M2, A + b.p2, ws, st, A + b.c2.w16));
             RC(train_act_pass(p, T, A, A + b.y2, b.bn2, b.c2.d.K, M2, A + b.p2, nullptr, -1, nullptr, A + b.a2, nullptr, true, st, nullptr));
             RC(conv_bn_train(p, T, b.c3, b.bn3, A + b.a2, nullptr, A, A + b.y3, A + b.s3, b.t3, b.r3, M2, A + b.p3, ws, st, A + b.c3.w16));
-            }
         } else {
         RC(conv_bn_train(p, T, b.c1, b.bn1, A + b.x, nullptr, A, A + b.y1, A + b.s1, b.t1, b.r1, M1, A + b.p1, ws, st));
         RC(conv_bn_train(p, T, b.c2, b.bn2, A + b.y1, A + b.p1, A, A + b.y2, A + b.s2, b.t2, b.r2, M2, A + b.p2, ws, st, nullptr, b.bn1, b.c1.d.K, M1));
@@ -659,17 +625,11 @@ struct SideCtx {
         return DPFT_OK;
     }
     // dy buffer `slot` is complete on the main stream: launch the weight gradient that reads it on the side stream
-    // `mat_y` (bf16 plan with operand prologues in the forward): x is relu(bn(mat_y)) and has not been materialised yet -- the
-    // elementwise pass runs here, on the stream of the weight gradient that wants it
-    int wgrad(int slot, const dpft_conv_desc* d, const float* x, const float* dy, const float* pro, int relu, float* dw,
-              const float* mat_y = nullptr, const float* mat_bnp = nullptr, int64_t mat_M = 0, int mat_K = 0) {
-        if (profiling_active()) {      // per-launch event timing wants each kernel alone on the device
-            if (mat_y) RC(bn_act_any(mat_y, mat_bnp, nullptr, nullptr, 1, const_cast<float*>(x), nullptr, mat_M, mat_K, true, (dpft_stream_t)main));
+    int wgrad(int slot, const dpft_conv_desc* d, const float* x, const float* dy, const float* pro, int relu, float* dw) {
+        if (profiling_active())      // per-launch event timing wants each kernel alone on the device
             return dpft_conv2d_nhwc_wgrad_f32(d, x, dy, pro, relu, dw, ws2, (dpft_stream_t)main);
-        }
         DPFT_REQUIRE(hipEventRecord(p->ev_ready, main) == hipSuccess, "resnet_backward: record event");
         DPFT_REQUIRE(hipStreamWaitEvent(p->side, p->ev_ready, 0) == hipSuccess, "resnet_backward: wait event");
-        if (mat_y) RC(bn_act_any(mat_y, mat_bnp, nullptr, nullptr, 1, const_cast<float*>(x), nullptr, mat_M, mat_K, true, (dpft_stream_t)p->side));
         RC(dpft_conv2d_nhwc_wgrad_f32(d, x, dy, pro, relu, dw, ws2, (dpft_stream_t)p->side));
         DPFT_REQUIRE(hipEventRecord(p->ev_done[slot], p->side) == hipSuccess, "resnet_backward: record event");
         p->ev_valid[slot] = true;
@@ -737,7 +697,7 @@ static int block_backward(ResnetPlan* p, const BlockPlan& b, const Tables& T, fl
     const unsigned char* m8 = (const unsigned char*)(A + b.mask);      // ReLU mask of the block output (written by the forward)
     RC(bn_backward(A + b.y3, gp, nullptr, nullptr, A + b.p3, T.gamma(b.bn3), sums, dyv[cur], T.dgamma(b.bn3), T.dbeta(b.bn3), M2, K3, st, a16, m8, bn3_reduced));
     const bool w16 = p->desc.act16 == 2;      // materialised activations a1 / a2: no prologue in the weight gradients either
-    if (w16) RC(sc.wgrad(cur, &b.c3.d, A + b.a2, dyv[cur], nullptr, 0, T.dw(b.c3.w), pro16_on() ? A + b.y2 : nullptr, A + b.p2, M2, planes));
+    if (w16) RC(sc.wgrad(cur, &b.c3.d, A + b.a2, dyv[cur], nullptr, 0, T.dw(b.c3.w)));
     else RC(sc.wgrad(cur, &b.c3.d, A + b.y2, dyv[cur], A + b.p2, 1, T.dw(b.c3.w)));
     // the data gradient of conv3 produces bn2's dout: bn2's reduction rides in its epilogue (mask = bn2(y2) > 0)
     BnReduceFuse f2{A + b.y2, A + b.p2, nullptr, 1, fuse_on ? sums.buf[sums.cur] : nullptr, false};
@@ -746,7 +706,7 @@ static int block_backward(ResnetPlan* p, const BlockPlan& b, const Tables& T, fl
     // bn2 (fused-ReLU mask recomputed from its BN block)
     RC(sc.acquire(cur));
     RC(bn_backward(A + b.y2, dab, nullptr, A + b.p2, A + b.p2, T.gamma(b.bn2), sums, dyv[cur], T.dgamma(b.bn2), T.dbeta(b.bn2), M2, planes, st, a16, nullptr, f2.applied));
-    if (w16) RC(sc.wgrad(cur, &b.c2.d, A + b.a1, dyv[cur], nullptr, 0, T.dw(b.c2.w), pro16_on() ? A + b.y1 : nullptr, A + b.p1, M1, planes));
+    if (w16) RC(sc.wgrad(cur, &b.c2.d, A + b.a1, dyv[cur], nullptr, 0, T.dw(b.c2.w)));
     else RC(sc.wgrad(cur, &b.c2.d, A + b.y1, dyv[cur], A + b.p1, 1, T.dw(b.c2.w)));
     BnReduceFuse f1{A + b.y1, A + b.p1, nullptr, 1, fuse_on ? sums.buf[sums.cur] : nullptr, false};
     RC(conv_dgrad_fused(&b.c2.d, dyv[cur], wt + b.c2.wt, dab, 0, ws, st, &f1));

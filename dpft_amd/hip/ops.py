@@ -208,10 +208,11 @@ def conv_fwd(cv: Conv, x, w, bias=None, pro=None, want_stats=False, out=None, pl
     y = out if out is not None else torch.empty((cv.B, cv.OH, cv.OW, cv.K), dtype=torch.float32, device=x.device)
     if out is not None and (tuple(out.shape) != (cv.B, cv.OH, cv.OW, cv.K) or not out.is_contiguous() or out.dtype != torch.float32):
         raise ValueError("conv_fwd: the output buffer does not match the problem")
-    stats = torch.empty((cv.tiles, 2, cv.K), dtype=torch.float32, device=x.device) if want_stats else None
     ws = workspace(cv.ws_bytes, x.device)
     pb, prelu = (pro[0], int(pro[1])) if pro is not None else (None, 0)
     with _with_planes(cv, planes):
+        # (the tiling depends on the planes: the streaming 1x1 kernel does not read them)
+        stats = torch.empty((cv.tiles, 2, cv.K), dtype=torch.float32, device=x.device) if want_stats else None
         lib.call("dpft_conv2d_nhwc_fwd_f32", C.byref(cv.desc), ptr(x), ptr(w), ptr(bias), ptr(pb), prelu,
                  ptr(y), ptr(stats), ptr(ws), stream())
     return y, stats

@@ -86,9 +86,6 @@ int dpft_split_planes_f32(const float* src, void* planes, int64_t n, dpft_stream
  * (rows of the `stats` buffer: stats is [mtiles][2][K] floats = per-tile mean and M2);
  * *tile_rows receives the tile height so the caller can recover per-tile counts. */
 int32_t dpft_conv2d_stats_tiles(const dpft_conv_desc* d, int32_t* tile_rows);
-/* the same for a launch that carries the BatchNorm + ReLU operand prologue (pro_bn != NULL in dpft_conv2d_nhwc_fwd_f32): with bf16
- * operands (act16 = 2) such a launch takes other tiles than the prologue-free one */
-int32_t dpft_conv2d_stats_tiles_pro(const dpft_conv_desc* d, int32_t pro, int32_t* tile_rows);
 
 /* Arithmetic of the forward / data-gradient GEMMs of every conv with C % 64 == 0 and of the 128 x 128-tiled weight
  * gradients (process-wide; call between launches):
@@ -115,7 +112,9 @@ int32_t dpft_conv_get_split(void);
 /* y[B,OH,OW,K] = conv(act(x), w) (+bias).  Optional fused prologue on the input operand:
  * act(x) = [max(., 0)] bn(x) with the PRODUCER's BN block pro_bn[4][C] (NULL = identity; pro_relu
  * selects the max).  Padding stays exactly zero.  Optional fused epilogue: per-M-tile per-channel
- * (mean, M2) of y into `stats` for train-mode BatchNorm (NULL to skip). */
+ * (mean, M2) of y into `stats` for train-mode BatchNorm (NULL to skip).  DPFT_ERR_ARG for bf16 weights (act16 = 2) with a bias
+ * or a prologue, and for statistics of a problem the streaming 1x1 kernel takes (the tiling dpft_conv2d_stats_tiles reports)
+ * together with a bias or a prologue without the ReLU. */
 int dpft_conv2d_nhwc_fwd_f32(const dpft_conv_desc* d, const float* x, const float* w,
                              const float* bias, const float* pro_bn, int32_t pro_relu, float* y,
                              float* stats, void* workspace, dpft_stream_t stream);

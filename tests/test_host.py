@@ -46,6 +46,20 @@ def test_cabi_argument_errors_are_reported():
     assert lib.dpft_conv_set_compute(3) == -1 and b"conv_set_compute" in lib.dpft_last_error()
     assert lib.dpft_conv_set_compute(1) == 0 and lib.dpft_conv_get_compute() == 1
     assert lib.dpft_conv_set_compute(0) == 0 and lib.dpft_conv_get_compute() == 0
+    # forward conv: combinations no kernel serves are refused before anything is launched (the pointers are never read)
+    from dpft_amd.hip.lib import make_desc
+    x, w, y, stats, bias, bnp, ws = (C.c_void_p(256 * (i + 1)) for i in range(7))
+    d = make_desc(8, 56, 56, 64, 256, 1, 1, 1, 0)           # a streaming 1x1 problem: its statistics come in that kernel's tiling
+    tr = C.c_int32(0)
+    assert lib.dpft_conv2d_stats_tiles(C.byref(d), C.byref(tr)) == -(-8 * 56 * 56 // tr.value)
+    rc = lib.dpft_conv2d_nhwc_fwd_f32(C.byref(d), x, w, bias, None, 0, y, stats, ws, None)
+    assert rc == -1 and b"streaming 1x1" in lib.dpft_last_error()
+    rc = lib.dpft_conv2d_nhwc_fwd_f32(C.byref(d), x, w, None, bnp, 0, y, stats, ws, None)
+    assert rc == -1 and b"streaming 1x1" in lib.dpft_last_error()
+    d16 = make_desc(2, 16, 16, 64, 128, 3, 3, 1, 1)
+    d16.act16 = 2                                             # bf16 weights: no operand prologue
+    rc = lib.dpft_conv2d_nhwc_fwd_f32(C.byref(d16), x, w, None, bnp, 1, y, None, ws, None)
+    assert rc == -1 and b"act16 = 2" in lib.dpft_last_error()
 
 
 def test_every_compute_entry_rejects_null_arguments():
