@@ -7,6 +7,9 @@
  *   - re-entrant and stream-ordered;
  *   - return 0 on success, a negative code otherwise; dpft_last_error() returns the message of
  *     the last failure on the calling thread (the Python side raises RuntimeError from it).
+ *   - sampling locations (dpft_msda_*, dpft_xattn_*, dpft_xattn_ffn_train_*, dpft_decoder_forward_f32) must be finite
+ *     and below 2^31 pixels in magnitude on every level: the fused decoders convert floor(t) to int before they
+ *     apply the in-map mask (sampling rule; tested out to 2^20 pixels on both sides).
  *
  * Reference interfaces replaced (paths relative to the TUMFTM/DPFT checkout):
  *   dpft_msda_fwd_f32 / dpft_msda_bwd_f32

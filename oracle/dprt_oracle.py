@@ -230,6 +230,40 @@ def msda_core(value, spatial_shapes, sampling_locations, attention_weights):
     return out.transpose(1, 2).contiguous()
 
 
+def msda_core_floor(value, spatial_shapes, sampling_locations, attention_weights):
+    """The sampling rule of the upstream im2col / col2im kernels written out once in differentiable torch
+    ops, same signature and result as ``msda_core``: ``t = loc * size - 0.5``; a sample counts iff ``-1 < t < size`` on both
+    axes (strictly); ``floor``; four corners, each masked by its own in-map test (zero padding); explicit weights.  ``floor``
+    carries no gradient, so autograd of this function IS the upstream backward rule: inside a cell the slope of that cell,
+    at an integer ``t`` the slope of the cell to its right (``floor(t) == t``), and 0 for ``t <= -1`` and ``t >= size``.
+    ``msda_core``'s grid_sample autograd agrees everywhere except on ``t == -1`` exactly, where it returns the one-sided
+    slope from inside the map (tests/test_sampler_rule.py pins that set)."""
+    N, S, M, D = value.shape
+    _, Lq, _, L, P, _ = sampling_locations.shape
+    out = value.new_zeros(N, Lq, M, D)
+    start = 0
+    for lid, (H, W) in enumerate(spatial_shapes):
+        H, W = int(H), int(W)
+        v = value[:, start:start + H * W].permute(0, 2, 1, 3)               # (N, M, H*W, D)
+        start += H * W
+        loc = sampling_locations[:, :, :, lid]                              # (N, Lq, M, P, 2) ordered (x, y)
+        a = attention_weights[:, :, :, lid]                                 # (N, Lq, M, P)
+        w_im, h_im = loc[..., 0] * W - 0.5, loc[..., 1] * H - 0.5
+        inside = (h_im > -1) & (w_im > -1) & (h_im < H) & (w_im < W)
+        hf, wf = torch.floor(h_im).detach(), torch.floor(w_im).detach()
+        lh, lw = h_im - hf, w_im - wf
+        hh, hw = 1 - lh, 1 - lw
+        h_lo, w_lo = hf.long(), wf.long()
+        for y, x, wgt in ((h_lo, w_lo, hh * hw), (h_lo, w_lo + 1, hh * lw),
+                          (h_lo + 1, w_lo, lh * hw), (h_lo + 1, w_lo + 1, lh * lw)):
+            ok = inside & (y >= 0) & (y <= H - 1) & (x >= 0) & (x <= W - 1)
+            idx = (y.clamp(0, H - 1) * W + x.clamp(0, W - 1)).permute(0, 2, 1, 3).reshape(N, M, Lq * P)
+            g = torch.gather(v, 2, idx[..., None].expand(N, M, Lq * P, D)).view(N, M, Lq, P, D).permute(0, 2, 1, 3, 4)
+            wk = torch.where(ok, wgt * a, torch.zeros_like(a))              # masked: no value and no slope from padding
+            out = out + (wk[..., None] * g).sum(3)
+    return out.reshape(N, Lq, M * D)
+
+
 def msda_core_scalar(value, spatial_shapes, level_start_index, loc, attn):
     """Pure-python restatement of the upstream im2col thread body (SURVEY App. C pseudo-code);
     small cases only.  Used to cross-check ``msda_core``."""
@@ -268,8 +302,9 @@ def msda_core_scalar(value, spatial_shapes, level_start_index, loc, attn):
 # MSDeformAttn.forward (src/dprt/models/layers/ms_deform_attn.py:138-217)
 # --------------------------------------------------------------------------- #
 def ms_deform_attn(query, ref_points_2d, levels_nhwc: List[torch.Tensor], sd, p: str,
-                   n_heads: int, n_points: int):
-    """query (B,Q,C) [already with pos]; ref (B,Q,2); levels: list of (B,H,W,C)."""
+                   n_heads: int, n_points: int, core=msda_core):
+    """query (B,Q,C) [already with pos]; ref (B,Q,2); levels: list of (B,H,W,C).  ``core``: ``msda_core`` (grid_sample,
+    what the golden fixtures were made with) or ``msda_core_floor`` (the kernels' rule, also on ``t == -1``)."""
     B, Q, C = query.shape
     L = len(levels_nhwc)
     shapes = [(l.shape[1], l.shape[2]) for l in levels_nhwc]
@@ -283,7 +318,7 @@ def ms_deform_attn(query, ref_points_2d, levels_nhwc: List[torch.Tensor], sd, p:
     normalizer = torch.tensor([[w, h] for h, w in shapes], dtype=query.dtype)     # (W_l, H_l) :186-188
     ref = ref_points_2d.unsqueeze(2).repeat(1, 1, L, 1)                          # mpfusion.py:190
     loc = ref[:, :, None, :, None, :] + off / normalizer[None, None, None, :, None, :]
-    out = msda_core(value, shapes, loc, aw)
+    out = core(value, shapes, loc, aw)
     return F.linear(out, sd[p + ".output_proj.weight"], sd[p + ".output_proj.bias"])
 
 

@@ -575,7 +575,9 @@ def test_fused_xattn_ffn_block_dropout_consistent():
     assert not torch.allclose(y_a, run(seed + 1, p))
     plist = [t for ml in layers for t in tf.view_params(ml)[6:]]
     flat_feats = [t for fv in feats for t in fv]
-    wrt = [y1, pos] + flat_feats + plist       # (refs: the bilinear kernel is only piecewise smooth)
+    # (refs: the bilinear kernel is only piecewise smooth -- a central difference across a kink is not a slope; which slope the
+    # kernels return there is pinned element by element in tests/test_gpu_sampler_edges.py)
+    wrt = [y1, pos] + flat_feats + plist
     gy = torch.randn_like(y_a)
     grads = torch.autograd.grad(y_a, wrt, gy)
     torch.manual_seed(4)
