@@ -1484,7 +1484,14 @@ static int launch_igemm(IgemmArgs& a, const TileChoice& t, bool pro, hipStream_t
     static const int ablate_env = getenv("DPFT_ABLATE") ? atoi(getenv("DPFT_ABLATE")) : 0;
     a.ablate = ablate_env;
     const bool nonlin = DGRAD && t.vec && a.stride > 1 && a.sub_step <= 1;
-    const int bm = nonlin ? 64 : t.bm, bn = nonlin ? 64 : t.bn;
+    // fp32, linear taps: the software-pipelined kernel (conv_pipe.h) -- LDS-DMA operands, one barrier per K-step.
+    // DPFT_PIPE=0 keeps igemm_vec_kernel (A/B measurements).
+    static const int pipe_env = getenv("DPFT_PIPE") ? atoi(getenv("DPFT_PIPE")) : 3;      // bit 0: igemm, bit 1: wgrad
+    const bool pipe = t.vec && g_conv_bf16 != 1 && (pipe_env & 1) && !a.x16 && !a.y16 && (!pro || a.pro_relu);
+    // a 64 x 128 tile (DPFT_FORCE_TILE only) exists in the pipelined fp32 kernel alone: every other kernel runs 64 x 64 tiles,
+    // and the grid is counted in those
+    const bool only64 = t.bm == 64 && t.bn == 128 && !pipe;
+    const int bm = nonlin ? 64 : t.bm, bn = (nonlin || only64) ? 64 : t.bn;
     a.mtiles = cdiv(a.M, bm);
     a.ntiles = cdiv(a.N, bn);
     a.splits = t.splits;
@@ -1494,6 +1501,7 @@ static int launch_igemm(IgemmArgs& a, const TileChoice& t, bool pro, hipStream_t
     dim3 grid(nwg), block(256);
     g_prof_family = !t.vec ? kFamVector : (g_conv_bf16 == 1 ? kFamBf16 : kFamF32);      // (the x3 branches below override)
     if (nonlin) {
+        g_prof_family = kFamF32;      // (the all-tap form has no bf16-operand variant: fp32 MFMA in every compute mode)
         if constexpr (DGRAD) {
             constexpr size_t lds = (size_t)(64 + 64) * LDK * sizeof(float);
             launch_lds(igemm_vec_kernel<64, 64, 2, 2, true, false, false>, grid, block, lds, st, a);
@@ -1541,10 +1549,7 @@ static int launch_igemm(IgemmArgs& a, const TileChoice& t, bool pro, hipStream_t
         g_prof_family = kFamX3;
         return launch_igemm_x3(a, t.bm, t.bn, DGRAD, pro, st);
     }
-    // fp32, linear taps: the software-pipelined kernel (conv_pipe.h) -- LDS-DMA operands, one barrier per K-step.
-    // DPFT_PIPE=0 keeps igemm_vec_kernel (A/B measurements).
-    static const int pipe_env = getenv("DPFT_PIPE") ? atoi(getenv("DPFT_PIPE")) : 3;      // bit 0: igemm, bit 1: wgrad
-    if (t.vec && g_conv_bf16 != 1 && (pipe_env & 1) && !a.x16 && !a.y16 && (!pro || a.pro_relu)) {
+    if (pipe) {
         g_prof_family = kFamF32;
         static const int shortk_env = getenv("DPFT_SHORTK") ? atoi(getenv("DPFT_SHORTK")) : 0;      // tuning aid
         const bool short_k = shortk_env > 0 && a.Ktot <= shortk_env;
@@ -1909,6 +1914,9 @@ extern "C" int dpft_conv2d_nhwc_fwd_bnact_f32(const dpft_conv_desc* d, const flo
     int rc = check_desc(d);
     if (rc) return rc;
     DPFT_REQUIRE(x && w && y && out_bn, "conv fwd_bnact: null tensor");
+    // (the epilogue form and the elementwise pass both take the output channels four at a time; refused here, before the
+    // convolution is launched, not by the pass behind it)
+    DPFT_REQUIRE(d->K % 4 == 0, "conv fwd_bnact: K %% 4 == 0 needed (K=%d)", d->K);
     hipStream_t st = (hipStream_t)stream;
     if (takes_stream1x1(d)) {
         ProfScope prof(0, d, st);
@@ -1920,7 +1928,7 @@ extern "C" int dpft_conv2d_nhwc_fwd_bnact_f32(const dpft_conv_desc* d, const flo
     if (d->act16) t.splits = 1;
     const int64_t M = (int64_t)d->B * d->OH * d->OW;
     static const bool fix_all = getenv("DPFT_BNACT_FIXUP") == nullptr || atoi(getenv("DPFT_BNACT_FIXUP")) != 0;      // A/B switch
-    if ((t.x3 || (fix_all && t.vec && !conv16_matches(d))) && t.splits > 1 && (a.N & 3) == 0 && workspace && sk_fixup_ok(a, t.splits, 1)) {
+    if ((t.x3 || (fix_all && t.vec && !conv16_matches(d))) && t.splits > 1 && workspace && sk_fixup_ok(a, t.splits, 1)) {
         // a K split (the latency-sized problems: batch-1 inference, the radar encoders' maps; the split kernels): the last
         // workgroup of a tile runs the whole inference epilogue (in-launch fix-up) -- no reduction launch, no elementwise pass
         ProfScope prof(0, d, st);
@@ -1930,7 +1938,7 @@ extern "C" int dpft_conv2d_nhwc_fwd_bnact_f32(const dpft_conv_desc* d, const flo
         a.obn = out_bn; a.oadd = residual; a.orelu = relu;
         return launch_igemm<false>(a, t, false, st);
     }
-    if (!t.vec || t.splits > 1 || (a.N & 3) != 0 || conv16_matches(d)) {
+    if (!t.vec || t.splits > 1 || conv16_matches(d)) {
         rc = dpft_conv2d_nhwc_fwd_f32(d, x, w, nullptr, nullptr, 0, y, nullptr, workspace, stream);
         if (rc) return rc;
         return bn_act_any(y, out_bn, residual, nullptr, relu, y, nullptr, M, d->K, d->act16 != 0, stream);
@@ -2188,6 +2196,8 @@ extern "C" int dpft_conv2d_nhwc_wgrad_f32(const dpft_conv_desc* d, const float* 
     int rc = check_desc(d);
     if (rc) return rc;
     DPFT_REQUIRE(x && dy && dw, "conv wgrad: null tensor");
+    DPFT_REQUIRE(!pro_bn || ((d->C % 32 == 0) && (d->K % 4 == 0)),
+                 "conv wgrad: fused prologue needs C %% 32 == 0 and K %% 4 == 0 (C=%d, K=%d)", d->C, d->K);
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof(2, d, st);
     if (!pro_bn) {
@@ -2206,7 +2216,6 @@ extern "C" int dpft_conv2d_nhwc_wgrad_f32(const dpft_conv_desc* d, const float* 
     const bool pro = pro_bn != nullptr;
     const bool vec = (d->C % 32 == 0) && (d->K % 4 == 0);
     a.psteps = cdiv(a.M, vec ? BKP : BK);
-    DPFT_REQUIRE(!(pro && !vec), "conv wgrad: fused prologue needs C %% 32 == 0");
     DPFT_REQUIRE(!vec || ((int64_t)a.M * a.K < (1ll << 29) && (int64_t)a.B * a.H * a.W * a.C < (1ll << 29)),
                  "conv wgrad: operand larger than 2 GiB");
     int bmn, bnc;

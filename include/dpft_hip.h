@@ -125,7 +125,8 @@ int dpft_conv2d_nhwc_fwd_f32(const dpft_conv_desc* d, const float* x, const floa
  * mode per conv (resnet.py Bottleneck: conv -> bn -> relu, and conv3 -> bn3 -> += identity -> relu; reached through
  * src/dprt/models/backbones/resnet.py:80-107):  y = [relu](bn(conv(x, w)) [+ residual]),  out_bn = BN block [4][K] of the
  * output channels (dpft_bn_eval_params_f32).  One launch where the problem takes the C % 64 == 0 path without split-K
- * (applied in the GEMM epilogue), otherwise the convolution followed by dpft_bn_act_f32 in place: same arithmetic. */
+ * (applied in the GEMM epilogue), otherwise the convolution followed by dpft_bn_act_f32 in place: same arithmetic.
+ * K % 4 == 0 (both forms take the output channels four at a time): DPFT_ERR_ARG otherwise, before anything is launched. */
 int dpft_conv2d_nhwc_fwd_bnact_f32(const dpft_conv_desc* desc, const float* x, const float* w, const float* out_bn,
                                    int32_t relu, const float* residual, float* y, void* workspace, dpft_stream_t stream);
 
@@ -152,7 +153,7 @@ int dpft_conv2d_nhwc_dgrad_bn_reduce_f32(const dpft_conv_desc* d, const float* d
                                          const uint8_t* bn_mask8, int32_t bn_self_mask, float* sums,
                                          int32_t* applied, void* workspace, dpft_stream_t stream);
 /* dw[K][kh][kw][C] = sum_pixels dy (x) act(x); same optional prologue on x as forward.
- * dw is overwritten. */
+ * dw is overwritten.  The prologue rides on the vector kernels only: C % 32 == 0 and K % 4 == 0, DPFT_ERR_ARG otherwise. */
 int dpft_conv2d_nhwc_wgrad_f32(const dpft_conv_desc* d, const float* x, const float* dy,
                                const float* pro_bn, int32_t pro_relu, float* dw, void* workspace,
                                dpft_stream_t stream);

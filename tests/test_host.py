@@ -60,6 +60,13 @@ def test_cabi_argument_errors_are_reported():
     d16.act16 = 2                                             # bf16 weights: no operand prologue
     rc = lib.dpft_conv2d_nhwc_fwd_f32(C.byref(d16), x, w, None, bnp, 1, y, None, ws, None)
     assert rc == -1 and b"act16 = 2" in lib.dpft_last_error()
+    # inference epilogue: the output channels come four at a time (found by the geometry lattice, tests/conv_lattice.py)
+    d66 = make_desc(2, 8, 8, 64, 66, 3, 3, 1, 1)
+    rc = lib.dpft_conv2d_nhwc_fwd_bnact_f32(C.byref(d66), x, w, bnp, 1, None, y, ws, None)
+    assert rc == -1 and b"conv fwd_bnact: K % 4 == 0 needed (K=66)" in lib.dpft_last_error()
+    # weight gradient: the operand prologue exists in the vector kernels only
+    rc = lib.dpft_conv2d_nhwc_wgrad_f32(C.byref(d66), x, y, bnp, 1, w, ws, None)
+    assert rc == -1 and b"conv wgrad: fused prologue needs C % 32 == 0 and K % 4 == 0 (C=64, K=66)" in lib.dpft_last_error()
 
 
 def test_every_compute_entry_rejects_null_arguments():
