@@ -733,9 +733,12 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
 // channels in every trip -- its five parameter quads are loaded once -- and keeps U element quads of both tensors in flight.
 // Why: inside the training step this pass shares its CUs with the weight-gradient stream's workgroups (the split kernels hold
 // 456 of a SIMD's 512 registers: ONE wave of this kernel fits beside them), and with one trip's two loads per wave in flight
-// it ran 2.3x slower there than alone (3.5 ms of the main queue, profiles/r06_bn_in_step.txt).  Stays within 56 registers so
-// that it still fits beside such a wave.  Same expression per element as bn_bwd_apply_kernel.
-template <int U>
+// it ran 2.3x slower there than alone (3.5 ms of the main queue, profiles/r06_bn_in_step.txt).  The forms the launch plan takes stay
+// within 56 registers so that they still fit beside such a wave: <1, *> 44 / 46 and the default <2, true> 56; <2, false> (a mask
+// recomputed from ANOTHER layer's block: C entry only) needs 58 and <3, *> (DPFT_BN_FIXC=3, an experiment switch) 66 / 70 -- the
+// amdgpu_num_vgpr attribute below is a request the compiler does not enforce.  Same value per element as bn_bwd_apply_kernel up to
+// rounding (see the constants below).
+template <int U, bool SAMEMU>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(56)))
 void bn_bwd_apply_fixc_kernel(const float* __restrict__ y, const float* __restrict__ dout, const float* __restrict__ outp,
                               const float* __restrict__ mbnp, const float* __restrict__ bnp, const float* __restrict__ gamma,
@@ -754,11 +757,15 @@ void bn_bwd_apply_fixc_kernel(const float* __restrict__ y, const float* __restri
     const unsigned stride = gridDim.x * blockDim.x;      // % K4 == 0 (host); n4 < 2^31 (host)
     const unsigned first = blockIdx.x * blockDim.x + threadIdx.x;
     const int c = (int)(first % (unsigned)K4) * 4;
-    // r = ga is (d - s0 / M - xhat s1 / M),  xhat = (y - mu) is   ==   A d + P + Q y  with three constants per channel
-    // (12 registers instead of 20 for the five parameter quads: the kernel has to stay within 56)
-    f32x4 A, P, Q;
+    // r = ga is (d - s0 / M - xhat s1 / M),  xhat = (y - mu) is   ==   A d + P + Q (y - mu)  with four constants per channel
+    // (16 registers instead of 20 for the five parameter quads: the kernel has to stay within 56).  y is centred BEFORE the
+    // multiply: with Q mu folded into P the roundings are relative to |Q y| and |Q mu|, which exceed |Q (y - mu)| by |mean| / std
+    // (tests/bn_lattice.py, float tier: thousands of times its bound at |mean| / std = 1000).
+    // SAMEMU: the ReLU mask is recomputed from the SAME BatchNorm block (mask_bnp == bnp, the launch plan's bn1 / bn2) -- its mean
+    // is mu and y - mu is at hand; only scale and shift of the mask's block are loaded (8 registers instead of 12)
+    f32x4 A, P, Q, mu;
     {
-        const f32x4 mu = *reinterpret_cast<const f32x4*>(bnp + c);
+        mu = *reinterpret_cast<const f32x4*>(bnp + c);
         const f32x4 is = *reinterpret_cast<const f32x4*>(bnp + 3 * K + c);
         const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + c);
         const f32x4 s0 = *reinterpret_cast<const f32x4*>(sums + c);
@@ -767,7 +774,7 @@ void bn_bwd_apply_fixc_kernel(const float* __restrict__ y, const float* __restri
         for (int e = 0; e < 4; ++e) {
             A[e] = ga[e] * is[e];
             Q[e] = -A[e] * is[e] * (s1[e] * invM);
-            P[e] = -A[e] * (s0[e] * invM) - Q[e] * mu[e];
+            P[e] = -A[e] * (s0[e] * invM);
         }
     }
     const unsigned n = (unsigned)n4;
@@ -797,20 +804,27 @@ void bn_bwd_apply_fixc_kernel(const float* __restrict__ y, const float* __restri
 #pragma unroll
                 for (int e = 0; e < 4; ++e) d[e] = o[e] > 0.f ? d[e] : 0.f;
             } else if (mbnp) {
-                const f32x4 a = bn_apply4(yv, mbnp, K, c);
+                if constexpr (SAMEMU) {      // bn_apply4 with the mean already in registers: the same expression
+                    const f32x4 msc = *reinterpret_cast<const f32x4*>(mbnp + K + c);
+                    const f32x4 mbe = *reinterpret_cast<const f32x4*>(mbnp + 2 * K + c);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) d[e] = a[e] > 0.f ? d[e] : 0.f;
+                    for (int e = 0; e < 4; ++e) d[e] = fmaf(yv[e] - mu[e], msc[e], mbe[e]) > 0.f ? d[e] : 0.f;
+                } else {
+                    const f32x4 a = bn_apply4(yv, mbnp, K, c);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) d[e] = a[e] > 0.f ? d[e] : 0.f;
+                }
             }
             f32x4 r;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) r[e] = fmaf(A[e], d[e], fmaf(Q[e], yv[e], P[e]));
+            for (int e = 0; e < 4; ++e) r[e] = fmaf(A[e], d[e], fmaf(Q[e], yv[e] - mu[e], P[e]));
             reinterpret_cast<f32x4*>(dy)[i] = r;
         }
     }
 }
 
 // BN backward pass 2, bf16 storage with 16-byte accesses (see bn_act16_kernel); K % 8 == 0
-template <bool FIXC>      // FIXC: as bn_act16_kernel (three precombined constants per channel, see bn_bwd_apply_fixc_kernel)
+template <bool FIXC>      // FIXC: as bn_act16_kernel (precombined constants per channel, y centred: see bn_bwd_apply_fixc_kernel)
 __global__ __launch_bounds__(256) void bn_bwd_apply16_kernel(const float* __restrict__ y, const float* __restrict__ dout,
                                                               const float* __restrict__ outp, const float* __restrict__ mbnp,
                                                               const float* __restrict__ bnp, const float* __restrict__ gamma,
@@ -833,7 +847,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply16_kernel(const float* __rest
     const u32x4_t* __restrict__ y8 = reinterpret_cast<const u32x4_t*>(y);
     const u32x4_t* __restrict__ o8 = reinterpret_cast<const u32x4_t*>(outp);
     const int cfix = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) % K8) * 8;
-    f32x4 cA[2], cP[2], cQ[2];
+    f32x4 cA[2], cP[2], cQ[2], cMu[2];
     if constexpr (FIXC) {
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
@@ -847,8 +861,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply16_kernel(const float* __rest
             for (int e = 0; e < 4; ++e) {
                 cA[hh][e] = ga[e] * is[e];
                 cQ[hh][e] = -cA[hh][e] * is[e] * (s1[e] * invM);
-                cP[hh][e] = -cA[hh][e] * (s0[e] * invM) - cQ[hh][e] * mu[e];
+                cP[hh][e] = -cA[hh][e] * (s0[e] * invM);
             }
+            cMu[hh] = mu;
         }
     }
     for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < n8; i0 += U * stride) {
@@ -890,7 +905,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply16_kernel(const float* __rest
                 }
                 if constexpr (FIXC) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) r[hh][e] = fmaf(cA[hh][e], d[hh][e], fmaf(cQ[hh][e], yv[hh][e], cP[hh][e]));
+                    for (int e = 0; e < 4; ++e) r[hh][e] = fmaf(cA[hh][e], d[hh][e], fmaf(cQ[hh][e], yv[hh][e] - cMu[hh][e], cP[hh][e]));
                 } else {
                     const f32x4 mu = *reinterpret_cast<const f32x4*>(bnp + c);
                     const f32x4 is = *reinterpret_cast<const f32x4*>(bnp + 3 * K + c);
@@ -1027,6 +1042,10 @@ static inline bool fixc_grid(int kq, int64_t items, int& blocks) {
     return true;
 }
 
+// which kernel form the dispatch below took at the last BatchNorm-family launch (dpft_bn_last_form): written where the launch is
+// made, never derived from the shape afterwards
+static int g_bn_last_form = DPFT_BN_FORM_NONE;
+
 static inline int ew_blocks(int64_t work_items) {
     static const int per_cu = getenv("DPFT_EW_BLOCKS_PER_CU") ? atoi(getenv("DPFT_EW_BLOCKS_PER_CU")) : 8;      // tuning aid
     return (int)std::max<int64_t>(1, std::min<int64_t>((work_items + 255) / 256, (int64_t)kNumCU * per_cu));
@@ -1095,17 +1114,20 @@ int dpft::bn_act_any(const float* y, const float* bnp, const float* res, const f
         ((uintptr_t)mask8 & 1) == 0)
     {
         int blocks = ew_blocks(n4 / 2);
-        if (fixc_grid(K / 8, n4 / 2, blocks))
+        const bool fx = fixc_grid(K / 8, n4 / 2, blocks);
+        g_bn_last_form = fx ? DPFT_BN_FORM_WIDE16_FIXC : DPFT_BN_FORM_WIDE16;
+        if (fx)
             hipLaunchKernelGGL(bn_act16_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, y, bnp, res, res_bnp, relu, out,
                                out32, n4 / 2, K / 8, mask8);
         else
             hipLaunchKernelGGL(bn_act16_kernel<false>, dim3(ew_blocks(n4 / 2)), dim3(256), 0, (hipStream_t)stream, y, bnp, res, res_bnp, relu, out,
                                out32, n4 / 2, K / 8, mask8);
     }
-    else if (act16)
+    else if (act16) {
+        g_bn_last_form = DPFT_BN_FORM_GENERIC;
         hipLaunchKernelGGL(bn_act_kernel<__bf16>, dim3(ew_blocks(n4)), dim3(256), 0, (hipStream_t)stream, y, bnp, res,
                            res_bnp, relu, out, out32, n4, K / 4, mask8);
-    else {
+    } else {
         static const int fixc = getenv("DPFT_BN_FIXC") ? atoi(getenv("DPFT_BN_FIXC")) : 2;      // see bn_bwd_apply_zeroing
         const int K4 = K / 4;
         static const int fat = getenv("DPFT_BN_FAT") ? atoi(getenv("DPFT_BN_FAT")) : 1;      // two quads per thread and trip (as bn_bwd_apply)
@@ -1116,6 +1138,7 @@ int dpft::bn_act_any(const float* y, const float* bnp, const float* res, const f
             ok = (K4 % 256) == 0 && blocks >= f;
             if (ok) blocks -= blocks % f;
         }
+        g_bn_last_form = !ok ? DPFT_BN_FORM_GENERIC : fixc >= 2 ? DPFT_BN_FORM_FIXC2 : DPFT_BN_FORM_FIXC1;
         if (ok && fixc >= 2)
             hipLaunchKernelGGL((bn_act_fixc_kernel<2, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, y, bnp, res, res_bnp, relu, out, n4,
                                K4, mask8, BnSumsRef{}, BnSumsRef{});
@@ -1149,6 +1172,7 @@ int dpft::bn_act_sums(const float* y, const float* bnp, const BnSumsRef& ys, con
         ok = (K4 % 256) == 0 && blocks >= f;
         if (ok) blocks -= blocks % f;
     }
+    g_bn_last_form = ok ? DPFT_BN_FORM_SUMS_TAKEN : DPFT_BN_FORM_SUMS_DECLINED;
     if (!ok) return DPFT_OK;      // (the generic kernel reads BN blocks only: the caller finalizes first)
     if (fixc >= 2)
         hipLaunchKernelGGL((bn_act_fixc_kernel<2, true>), dim3(blocks), dim3(256), K4 < 256 ? (size_t)24 * K : 0, (hipStream_t)stream, y, bnp, res,
@@ -1201,6 +1225,7 @@ int dpft::bn_relu_maxpool_any(const float* y, const float* bnp, float* out, int3
     DPFT_REQUIRE(y && bnp && out && K % 4 == 0, "bn_relu_maxpool: bad arguments");
     DPFT_REQUIRE(PH == (H + 2 - 3) / 2 + 1 && PW == (W + 2 - 3) / 2 + 1, "bn_relu_maxpool: PH/PW inconsistent");
     const int64_t total = (int64_t)B * PH * PW * (K / 4);
+    g_bn_last_form = DPFT_BN_FORM_GENERIC;
     if (out16)
         hipLaunchKernelGGL(bn_relu_maxpool_kernel<__bf16>, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, y, bnp,
                            out, B, H, W, K / 4, PH, PW);
@@ -1226,6 +1251,7 @@ int dpft::bn_relu_maxpool_bwd_any(const float* y, const float* bnp, const float*
         const int tiles_h = cdiv(H, 2 * PB_TH), tiles_w = cdiv(W, 2 * PB_TW);
         const int64_t nb = (int64_t)B * (K4 / PB_CQ) * tiles_h * tiles_w;
         DPFT_REQUIRE(nb < (1ll << 31), "bn_relu_maxpool_bwd: too many tiles");
+        g_bn_last_form = DPFT_BN_FORM_POOL_TILED;
         if (dout16)
             hipLaunchKernelGGL(bn_relu_maxpool_bwd_tiled_kernel<__bf16>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, y, bnp,
                                dout, dact, B, H, W, K4, PH, PW, tiles_w, tiles_h);
@@ -1234,6 +1260,7 @@ int dpft::bn_relu_maxpool_bwd_any(const float* y, const float* bnp, const float*
                                dout, dact, B, H, W, K4, PH, PW, tiles_w, tiles_h);
         return check_launch("bn_relu_maxpool_bwd (tiled)");
     }
+    g_bn_last_form = DPFT_BN_FORM_GENERIC;
     if (dout16)
         hipLaunchKernelGGL(bn_relu_maxpool_bwd_kernel<__bf16>, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, y,
                            bnp, dout, dact, B, H, W, K / 4, PH, PW);
@@ -1273,6 +1300,7 @@ int dpft::bn_bwd_reduce_prezeroed(const float* y, const float* dout, const float
     const int want_blocks = std::min(64, std::max(1, (kNumCU * 4) / slabs));
     int64_t rows_per_block = std::max<int64_t>((int64_t)groups * 4, (M + want_blocks - 1) / want_blocks);
     dim3 grid(cdiv(M, rows_per_block), slabs);
+    g_bn_last_form = DPFT_BN_FORM_GENERIC;
     if (act16)
         hipLaunchKernelGGL(bn_bwd_reduce_kernel<__bf16>, grid, dim3(256), 0, st, y, dout, out, mask_bnp, bnp, sums, M, K,
                            (int)rows_per_block, slab, mask8);
@@ -1307,17 +1335,20 @@ int dpft::bn_bwd_apply_zeroing(const float* y, const float* dout, const float* o
         ((uintptr_t)out & 15) == 0 && ((uintptr_t)mask8 & 1) == 0)
     {
         int blocks = ew_blocks(n4 / 2);
-        if (fixc_grid(K / 8, n4 / 2, blocks))
+        const bool fx = fixc_grid(K / 8, n4 / 2, blocks);
+        g_bn_last_form = fx ? DPFT_BN_FORM_WIDE16_FIXC : DPFT_BN_FORM_WIDE16;
+        if (fx)
             hipLaunchKernelGGL(bn_bwd_apply16_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, y, dout, out, mask_bnp, bnp,
                                gamma, sums, dy, dgamma, dbeta, n4 / 2, K, invM, zero_buf, (int)zero_n, mask8);
         else
             hipLaunchKernelGGL(bn_bwd_apply16_kernel<false>, dim3(ew_blocks(n4 / 2)), dim3(256), 0, (hipStream_t)stream, y, dout, out, mask_bnp, bnp,
                                gamma, sums, dy, dgamma, dbeta, n4 / 2, K, invM, zero_buf, (int)zero_n, mask8);
     }
-    else if (act16)
+    else if (act16) {
+        g_bn_last_form = DPFT_BN_FORM_GENERIC;
         hipLaunchKernelGGL(bn_bwd_apply_kernel<__bf16>, dim3(ew_blocks(n4)), dim3(256), 0, (hipStream_t)stream, y, dout, out,
                            mask_bnp, bnp, gamma, sums, dy, dgamma, dbeta, n4, K, invM, zero_buf, (int)zero_n, mask8);
-    else {
+    } else {
         // fixed-channel form (see bn_bwd_apply_fixc_kernel): the grid stride must be a multiple of K / 4.  DPFT_BN_FIXC=0: off; =U: quads in flight
         static const int fixc = getenv("DPFT_BN_FIXC") ? atoi(getenv("DPFT_BN_FIXC")) : 2;
         const int K4 = K / 4;
@@ -1331,15 +1362,18 @@ int dpft::bn_bwd_apply_zeroing(const float* y, const float* dout, const float* o
             ok = (K4 % 256) == 0 && blocks >= f;
             if (ok) blocks -= blocks % f;
         }
-        if (ok && fixc >= 3)
-            hipLaunchKernelGGL(bn_bwd_apply_fixc_kernel<3>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, y, dout, out, mask_bnp, bnp,
-                               gamma, sums, dy, dgamma, dbeta, n4, K, invM, zero_buf, (int)zero_n, mask8);
-        else if (ok && fixc == 2)
-            hipLaunchKernelGGL(bn_bwd_apply_fixc_kernel<2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, y, dout, out, mask_bnp, bnp,
-                               gamma, sums, dy, dgamma, dbeta, n4, K, invM, zero_buf, (int)zero_n, mask8);
-        else if (ok)
-            hipLaunchKernelGGL(bn_bwd_apply_fixc_kernel<1>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, y, dout, out, mask_bnp, bnp,
-                               gamma, sums, dy, dgamma, dbeta, n4, K, invM, zero_buf, (int)zero_n, mask8);
+        g_bn_last_form = !ok ? DPFT_BN_FORM_GENERIC : fixc >= 3 ? DPFT_BN_FORM_FIXC3 : fixc == 2 ? DPFT_BN_FORM_FIXC2 : DPFT_BN_FORM_FIXC1;
+        // the kernel reads mask_bnp only where neither mask8 nor out is given: the general form only for a mask from ANOTHER block
+        const bool same = mask_bnp == bnp || !mask_bnp || mask8 || out;
+        auto launch = [&](auto u) {
+            constexpr int U = decltype(u)::value;
+            auto kernel = same ? bn_bwd_apply_fixc_kernel<U, true> : bn_bwd_apply_fixc_kernel<U, false>;
+            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, y, dout, out, mask_bnp, bnp, gamma, sums, dy,
+                               dgamma, dbeta, n4, K, invM, zero_buf, (int)zero_n, mask8);
+        };
+        if (ok && fixc >= 3) launch(std::integral_constant<int, 3>{});
+        else if (ok && fixc == 2) launch(std::integral_constant<int, 2>{});
+        else if (ok) launch(std::integral_constant<int, 1>{});
         else
             hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3(ew_blocks(n4)), dim3(256), 0, (hipStream_t)stream, y, dout, out,
                                mask_bnp, bnp, gamma, sums, dy, dgamma, dbeta, n4, K, invM, zero_buf, (int)zero_n, mask8);
@@ -1355,6 +1389,7 @@ extern "C" int dpft_relu_bwd_f32(const float* dout, const float* out, float* dz,
 
 int dpft::add_inplace_any(float* a, const float* b, int64_t n, bool a16, dpft_stream_t stream) {
     DPFT_REQUIRE(a && b && n > 0 && (!a16 || n % 4 == 0), "add_inplace: bad arguments");
+    g_bn_last_form = DPFT_BN_FORM_GENERIC;
     if (a16) hipLaunchKernelGGL(add_inplace_kernel<__bf16>, dim3(ew_blocks(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, a, b, n);
     else hipLaunchKernelGGL(add_inplace_kernel<float>, dim3(ew_blocks(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, a, b, n);
     return check_launch("add_inplace");
@@ -1366,8 +1401,98 @@ extern "C" int dpft_add_inplace_f32(float* a, const float* b, int64_t n, dpft_st
 
 int dpft::cvt_f32_to_bf16(const float* src, float* dst_bf16, int64_t n, dpft_stream_t stream) {
     DPFT_REQUIRE(src && dst_bf16 && n > 0 && n % 4 == 0, "cvt_f32_to_bf16: bad arguments");
+    g_bn_last_form = DPFT_BN_FORM_GENERIC;
     hipLaunchKernelGGL(cvt_f32_bf16_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, src, dst_bf16, n / 4);
     return check_launch("cvt_f32_to_bf16");
+}
+
+// ---------------------------------------------------------------------------------------------
+// Storage-typed entries (include/dpft_hip.h): the workers above, unchanged, with every optional argument the launch plan passes
+// them.  What a worker would accept and then read or write out of bounds is refused here.
+// ---------------------------------------------------------------------------------------------
+#define DPFT_BN_STORAGE(what, s) DPFT_REQUIRE((s) == 0 || (s) == 1, what ": storage must be 0 (fp32) or 1 (bf16), got %d", (int)(s))
+// a lane's access is one quad: 16 bytes of fp32, 8 bytes of bf16 (the 16-byte bf16 forms test their own alignment and fall back)
+static inline bool quad_aligned(const void* p, int32_t storage) { return ((uintptr_t)p & (storage ? 7 : 15)) == 0; }
+
+extern "C" int dpft_bn_act_any_f32(const void* y, const float* bnp, const void* res, const float* res_bnp, int32_t relu, void* out,
+                                   float* out32, uint8_t* mask8, int64_t M, int32_t K, int32_t storage, dpft_stream_t stream) {
+    DPFT_BN_STORAGE("bn_act", storage);
+    DPFT_REQUIRE(M <= 0 || K <= 0 || M < (1ll << 40) / K, "bn_act: M * K too large");
+    DPFT_REQUIRE(quad_aligned(y, storage) && quad_aligned(res, storage) && quad_aligned(out, storage) && quad_aligned(out32, 0),
+                 "bn_act: tensors must be aligned to 4 elements");
+    return dpft::bn_act_any((const float*)y, bnp, (const float*)res, res_bnp, relu, (float*)out, out32, M, K, storage != 0, stream, mask8);
+}
+
+extern "C" int dpft_bn_act_sums_f32(const float* y, const float* bnp, const uint64_t* y_sums, const float* y_gamma, const float* y_beta,
+                                    const float* res, const float* res_bnp, const uint64_t* res_sums, const float* res_gamma,
+                                    const float* res_beta, float eps, int32_t relu, float* out, uint8_t* mask8, int64_t M,
+                                    int32_t K, int32_t* used, dpft_stream_t stream) {
+    DPFT_REQUIRE(used, "bn_act (column sums): used is null");
+    *used = 0;
+    DPFT_REQUIRE(!y_sums || (y_gamma && y_beta), "bn_act (column sums): y sums without gamma / beta");
+    DPFT_REQUIRE(!res_sums || (res_gamma && res_beta), "bn_act (column sums): residual sums without gamma / beta");
+    DPFT_REQUIRE(M > 0 && eps >= 0.f, "bn_act (column sums): M > 0 and eps >= 0 needed");
+    const double invn = 1.0 / (double)M;      // the sums are over the M rows of the pass
+    const BnSumsRef ys{(const unsigned long long*)y_sums, y_gamma, y_beta, invn, eps, K};
+    const BnSumsRef rs{(const unsigned long long*)res_sums, res_gamma, res_beta, invn, eps, K};
+    bool u = false;
+    const int rc = dpft::bn_act_sums(y, bnp, ys, res, res_bnp, rs, relu, out, M, K, stream, mask8, &u);
+    *used = u ? 1 : 0;
+    return rc;
+}
+
+extern "C" int dpft_bn_bwd_reduce_any_f32(const void* y, const void* dout, const void* out, const float* mask_bnp, const uint8_t* mask8,
+                                          const float* bnp, float* sums, int64_t M, int32_t K, int32_t storage, dpft_stream_t stream) {
+    DPFT_BN_STORAGE("bn_bwd_reduce", storage);
+    DPFT_REQUIRE(y && dout && bnp && sums && M > 0 && K > 0 && K % 4 == 0, "bn_bwd_reduce: bad arguments");
+    DPFT_REQUIRE(hipMemsetAsync(sums, 0, sizeof(float) * 2 * K, (hipStream_t)stream) == hipSuccess, "bn_bwd_reduce: memset failed");
+    return dpft::bn_bwd_reduce_prezeroed((const float*)y, (const float*)dout, (const float*)out, mask_bnp, bnp, sums, M, K, storage != 0,
+                                         stream, mask8);
+}
+
+extern "C" int dpft_bn_bwd_apply_any_f32(const void* y, const void* dout, const void* out, const float* mask_bnp, const uint8_t* mask8,
+                                         const float* bnp, const float* gamma, const float* sums, void* dy, float* dgamma, float* dbeta,
+                                         float* zero_buf, int32_t zero_n, int64_t M, int32_t K, int32_t storage, int32_t frozen,
+                                         dpft_stream_t stream) {
+    DPFT_BN_STORAGE("bn_bwd_apply", storage);
+    DPFT_REQUIRE(K > 0, "bn_bwd_apply: bad arguments (K=%d)", K);
+    DPFT_REQUIRE(zero_n >= 0 && (zero_n == 0 || zero_buf), "bn_bwd_apply: zero_n = %d with zero_buf %s", zero_n, zero_buf ? "set" : "null");
+    DPFT_REQUIRE(zero_buf != sums || zero_n == 0, "bn_bwd_apply: zero_buf must not be the sums this pass reads");
+    DPFT_REQUIRE(quad_aligned(y, storage) && quad_aligned(dout, storage) && quad_aligned(out, storage) && quad_aligned(dy, storage),
+                 "bn_bwd_apply: tensors must be aligned to 4 elements");
+    return dpft::bn_bwd_apply_zeroing((const float*)y, (const float*)dout, (const float*)out, mask_bnp, bnp, gamma, sums, (float*)dy,
+                                      dgamma, dbeta, M, K, zero_buf, zero_n, storage != 0, stream, mask8, frozen != 0);
+}
+
+extern "C" int dpft_bn_relu_maxpool_any_f32(const float* y, const float* bnp, void* out, int32_t B, int32_t H, int32_t W, int32_t K,
+                                            int32_t PH, int32_t PW, int32_t storage, dpft_stream_t stream) {
+    DPFT_BN_STORAGE("bn_relu_maxpool", storage);
+    DPFT_REQUIRE(B > 0 && H > 0 && W > 0 && K > 0, "bn_relu_maxpool: bad arguments");
+    return dpft::bn_relu_maxpool_any(y, bnp, (float*)out, B, H, W, K, PH, PW, storage != 0, stream);
+}
+
+extern "C" int dpft_bn_relu_maxpool_bwd_any_f32(const float* y, const float* bnp, const void* dout, float* dz, int32_t B, int32_t H,
+                                                int32_t W, int32_t K, int32_t PH, int32_t PW, int32_t storage, dpft_stream_t stream) {
+    DPFT_BN_STORAGE("bn_relu_maxpool_bwd", storage);
+    DPFT_REQUIRE(B > 0 && H > 0 && W > 0 && K > 0, "bn_relu_maxpool_bwd: bad arguments");
+    // the worker checks the window geometry on its tiled branch only; the gather form would read dout past a smaller pooled map
+    DPFT_REQUIRE(PH == (H - 1) / 2 + 1 && PW == (W - 1) / 2 + 1, "bn_relu_maxpool_bwd: PH/PW inconsistent");
+    return dpft::bn_relu_maxpool_bwd_any(y, bnp, (const float*)dout, dz, B, H, W, K, PH, PW, storage != 0, stream);
+}
+
+extern "C" int dpft_add_inplace_any_f32(void* a, const float* b, int64_t n, int32_t storage, dpft_stream_t stream) {
+    DPFT_BN_STORAGE("add_inplace", storage);
+    return dpft::add_inplace_any((float*)a, b, n, storage != 0, stream);
+}
+
+extern "C" int dpft_cvt_f32_bf16(const float* src, void* dst, int64_t n, dpft_stream_t stream) {
+    return dpft::cvt_f32_to_bf16(src, (float*)dst, n, stream);
+}
+
+extern "C" int dpft_bn_last_form(int32_t* form) {
+    DPFT_REQUIRE(form, "bn_last_form: form is null");
+    *form = g_bn_last_form;
+    return DPFT_OK;
 }
 
 extern "C" int dpft_fpn_topdown_add_f32(float* lat, const float* top, int32_t B, int32_t H, int32_t W,

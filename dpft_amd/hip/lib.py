@@ -122,6 +122,15 @@ SIGNATURES = {
     "dpft_bn_bwd_apply_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P]),
     "dpft_relu_bwd_f32": (_I, [_P, _P, _P, _L, _P]),
     "dpft_add_inplace_f32": (_I, [_P, _P, _L, _P]),
+    "dpft_bn_act_any_f32": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _L, _I, _I, _P]),
+    "dpft_bn_act_sums_f32": (_I, [_P] * 10 + [_F, _I, _P, _P, _L, _I, C.POINTER(_I), _P]),
+    "dpft_bn_bwd_reduce_any_f32": (_I, [_P] * 7 + [_L, _I, _I, _P]),
+    "dpft_bn_bwd_apply_any_f32": (_I, [_P] * 12 + [_I, _L, _I, _I, _I, _P]),
+    "dpft_bn_relu_maxpool_any_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "dpft_bn_relu_maxpool_bwd_any_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "dpft_add_inplace_any_f32": (_I, [_P, _P, _L, _I, _P]),
+    "dpft_cvt_f32_bf16": (_I, [_P, _P, _L, _P]),
+    "dpft_bn_last_form": (_I, [C.POINTER(_I)]),
     "dpft_fpn_topdown_add_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dpft_fpn_topdown_add_bwd_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dpft_add_pos_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),

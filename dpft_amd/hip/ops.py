@@ -10,7 +10,7 @@ from typing import Optional, Sequence, Tuple
 
 import torch
 
-from dpft_amd.hip.lib import ConvDesc, lib, make_desc, make_pyramid, ptr, stream
+from dpft_amd.hip.lib import ConvDesc, HipLibraryError, lib, make_desc, make_pyramid, ptr, stream
 
 _ws_cache = {}
 
@@ -412,6 +412,91 @@ def relu_bwd(dout, out):
 def add_(a, b):
     lib.call("dpft_add_inplace_f32", ptr(a), ptr(b), a.numel(), stream())
     return a
+
+
+# The BatchNorm passes with their storage type and optional tensors (dpft_*_any_f32): what the native launch plan calls inside the
+# library, one pass at a time.  bf16 tensors travel as torch.bfloat16 tensors.
+BN_FORMS = ("none", "generic", "fixc1", "fixc2", "fixc3", "wide16", "wide16_fixc", "pool_tiled", "sums_taken", "sums_declined")
+
+
+def bn_last_form() -> str:
+    """The kernel form the library's dispatch took at its last BatchNorm-family launch (dpft_bn_last_form)."""
+    form = C.c_int32(-1)
+    lib.call("dpft_bn_last_form", C.byref(form))
+    return BN_FORMS[form.value]
+
+
+def _storage(t: torch.Tensor) -> int:
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        raise HipLibraryError(f"activation storage is float32 or bfloat16, not {t.dtype}")
+    return int(t.dtype == torch.bfloat16)
+
+
+def bn_act_any(y, bnp, res=None, res_bnp=None, relu=True, out=None, out32=None, mask8=None):
+    """out = [relu](bn(y) [+ bn_res(res) | + res]) in y's storage type; writes the optional fp32 copy and mask bytes given."""
+    out = torch.empty_like(y) if out is None else out
+    K = y.shape[-1]
+    lib.call("dpft_bn_act_any_f32", ptr(y), ptr(bnp), ptr(res), ptr(res_bnp), int(relu), ptr(out), ptr(out32), ptr(mask8),
+             y.numel() // K, K, _storage(y), stream())
+    return out
+
+
+def bn_act_sums(y, bnp=None, y_sums=None, y_gamma=None, y_beta=None, res=None, res_bnp=None, res_sums=None, res_gamma=None,
+                res_beta=None, eps=1e-5, relu=True, out=None, mask8=None):
+    """The fp32 pass with either BatchNorm as column sums ((4, K) int64 words).  Returns (out, used); used False = nothing launched."""
+    out = torch.empty_like(y) if out is None else out
+    K = y.shape[-1]
+    M = y.numel() // K
+    used = C.c_int32(0)
+    lib.call("dpft_bn_act_sums_f32", ptr(y), ptr(bnp), ptr(y_sums), ptr(y_gamma), ptr(y_beta), ptr(res), ptr(res_bnp),
+             ptr(res_sums), ptr(res_gamma), ptr(res_beta), float(eps), int(relu), ptr(out), ptr(mask8), M, K,
+             C.byref(used), stream())
+    return out, bool(used.value)
+
+
+def bn_bwd_reduce_any(y, dout, bnp, out=None, mask_bnp=None, mask8=None, sums=None):
+    K = y.shape[-1]
+    sums = torch.empty((2, K), dtype=torch.float32, device=y.device) if sums is None else sums
+    lib.call("dpft_bn_bwd_reduce_any_f32", ptr(y), ptr(dout), ptr(out), ptr(mask_bnp), ptr(mask8), ptr(bnp), ptr(sums),
+             y.numel() // K, K, _storage(y), stream())
+    return sums
+
+
+def bn_bwd_apply_any(y, dout, bnp, gamma, sums, out=None, mask_bnp=None, mask8=None, frozen=False, dy=None, dgamma=None,
+                     dbeta=None, zero_buf=None):
+    K = y.shape[-1]
+    dy = torch.empty_like(y) if dy is None else dy
+    lib.call("dpft_bn_bwd_apply_any_f32", ptr(y), ptr(dout), ptr(out), ptr(mask_bnp), ptr(mask8), ptr(bnp), ptr(gamma),
+             ptr(sums), ptr(dy), ptr(dgamma), ptr(dbeta), ptr(zero_buf), 0 if zero_buf is None else zero_buf.numel(),
+             y.numel() // K, K, _storage(y), int(frozen), stream())
+    return dy
+
+
+def bn_relu_maxpool_any(y, bnp, dtype=torch.float32, out=None):
+    B, H, W, K = y.shape
+    PH, PW = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
+    out = torch.empty((B, PH, PW, K), dtype=dtype, device=y.device) if out is None else out
+    lib.call("dpft_bn_relu_maxpool_any_f32", ptr(y), ptr(bnp), ptr(out), B, H, W, K, PH, PW, _storage(out), stream())
+    return out
+
+
+def bn_relu_maxpool_bwd_any(y, bnp, dout, dz=None):
+    B, H, W, K = y.shape
+    dz = torch.empty_like(y) if dz is None else dz
+    lib.call("dpft_bn_relu_maxpool_bwd_any_f32", ptr(y), ptr(bnp), ptr(dout), ptr(dz), B, H, W, K, dout.shape[1], dout.shape[2],
+             _storage(dout), stream())
+    return dz
+
+
+def add_any_(a, b):
+    lib.call("dpft_add_inplace_any_f32", ptr(a), ptr(b), a.numel(), _storage(a), stream())
+    return a
+
+
+def cvt_f32_bf16(src, out=None):
+    out = torch.empty_like(src, dtype=torch.bfloat16) if out is None else out
+    lib.call("dpft_cvt_f32_bf16", ptr(src), ptr(out), src.numel(), stream())
+    return out
 
 
 def fpn_topdown_add_(lat, top):

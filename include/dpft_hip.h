@@ -216,6 +216,59 @@ int dpft_relu_bwd_f32(const float* dout, const float* out, float* dz, int64_t n,
 /* a += b */
 int dpft_add_inplace_f32(float* a, const float* b, int64_t n, dpft_stream_t stream);
 
+/* The same passes with everything the launch plan passes its workers, so that every kernel form can be driven alone (the
+ * entries above are these with storage = 0 and no optional tensor).
+ *   storage   0: the activation / gradient tensors (y, res, out, dout, dy) are fp32; 1: bf16 (mixed-precision storage).  BN
+ *             blocks, sums, parameter gradients, out32 and masks keep their types; all arithmetic is fp32 either way.
+ *   mask8     [M][K/4] bytes, bit e of a byte = element e of its 4 channels is > 0 in `out`: written by the forward pass, read
+ *             by the backward passes INSTEAD of `out` (precedence: mask8, then out, then mask_bnp).
+ *   out32     optional fp32 copy of `out` (bf16 storage: the unrounded values).
+ * Refused with DPFT_ERR_ARG: K % 4 != 0, null tensors, res_bnp without res, a storage other than 0 / 1, tensors that are not
+ * aligned to 4 elements. */
+int dpft_bn_act_any_f32(const void* y, const float* bnp, const void* res, const float* res_bnp, int32_t relu, void* out,
+                        float* out32, uint8_t* mask8, int64_t M, int32_t K, int32_t storage, dpft_stream_t stream);
+/* fp32 tensors; either BatchNorm given as column sums instead of a BN block: y_sums / res_sums are [4][K] 64-bit words, the
+ * 96-bit fixed-point accumulators the forward convs add to (sum y: high word counting fours, low word in units of 2^-46; then
+ * sum y^2 the same way) over the M rows, with the layer's gamma / beta; eps shared by both.  A null sums pointer = take that
+ * side's BN block.  *used = 0 and NOTHING launched (out untouched) where only the generic kernel fits the shape: the caller
+ * finalizes the sums into BN blocks and calls dpft_bn_act_f32. */
+int dpft_bn_act_sums_f32(const float* y, const float* bnp, const uint64_t* y_sums, const float* y_gamma, const float* y_beta,
+                         const float* res, const float* res_bnp, const uint64_t* res_sums, const float* res_gamma,
+                         const float* res_beta, float eps, int32_t relu, float* out, uint8_t* mask8, int64_t M,
+                         int32_t K, int32_t* used, dpft_stream_t stream);
+/* pass 1 (sums [2][K] cleared by the entry) */
+int dpft_bn_bwd_reduce_any_f32(const void* y, const void* dout, const void* out, const float* mask_bnp, const uint8_t* mask8,
+                               const float* bnp, float* sums, int64_t M, int32_t K, int32_t storage, dpft_stream_t stream);
+/* pass 2.  frozen != 0: running-statistics BatchNorm, dy = gamma * invstd * dz (no mean terms); dgamma / dbeta (either may be
+ * null) are copied from the sums in both modes.  zero_buf[0..zero_n) is cleared by the same launch (the launch plan's other
+ * accumulator); it must not be `sums`. */
+int dpft_bn_bwd_apply_any_f32(const void* y, const void* dout, const void* out, const float* mask_bnp, const uint8_t* mask8,
+                              const float* bnp, const float* gamma, const float* sums, void* dy, float* dgamma, float* dbeta,
+                              float* zero_buf, int32_t zero_n, int64_t M, int32_t K, int32_t storage, int32_t frozen,
+                              dpft_stream_t stream);
+/* stem pool: y and dz fp32; storage is the type of the pooled tensors `out` / `dout` */
+int dpft_bn_relu_maxpool_any_f32(const float* y, const float* bnp, void* out, int32_t B, int32_t H, int32_t W, int32_t K,
+                                 int32_t PH, int32_t PW, int32_t storage, dpft_stream_t stream);
+int dpft_bn_relu_maxpool_bwd_any_f32(const float* y, const float* bnp, const void* dout, float* dz, int32_t B, int32_t H,
+                                     int32_t W, int32_t K, int32_t PH, int32_t PW, int32_t storage, dpft_stream_t stream);
+/* a (storage type) += b (fp32); bf16: n % 4 == 0, one rounding to nearest even of the fp32 sum */
+int dpft_add_inplace_any_f32(void* a, const float* b, int64_t n, int32_t storage, dpft_stream_t stream);
+/* dst (bf16) = src (fp32), round to nearest even; n % 4 == 0 */
+int dpft_cvt_f32_bf16(const float* src, void* dst, int64_t n, dpft_stream_t stream);
+/* The kernel form the dispatch took at the last launch of this family in the process, written by the dispatch code at the
+ * launch (not derived from the shape; as dpft_profile_get_family).  Not thread-safe: a test aid. */
+#define DPFT_BN_FORM_NONE 0
+#define DPFT_BN_FORM_GENERIC 1          /* channel index per element: every fp32 / 8-byte bf16 kernel, gather pool, reduce */
+#define DPFT_BN_FORM_FIXC1 2            /* fp32 fixed-channel, 1 quad per thread and trip */
+#define DPFT_BN_FORM_FIXC2 3
+#define DPFT_BN_FORM_FIXC3 4
+#define DPFT_BN_FORM_WIDE16 5           /* bf16 with 16-byte accesses */
+#define DPFT_BN_FORM_WIDE16_FIXC 6
+#define DPFT_BN_FORM_POOL_TILED 7       /* tiled max-pool backward */
+#define DPFT_BN_FORM_SUMS_TAKEN 8       /* dpft_bn_act_sums_f32 launched its kernel */
+#define DPFT_BN_FORM_SUMS_DECLINED 9    /* ... or left the pass to the caller */
+int dpft_bn_last_form(int32_t* form);
+
 /* ------------------------------------------------------------------------------------------
  * Native launch plan of the ResNet body (conv1/bn1/relu/maxpool/layer1..n of torchvision's
  * ResNet-50/101/152 behind IntermediateLayerGetter, src/dprt/models/backbones/resnet.py:54-55,

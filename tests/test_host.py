@@ -69,6 +69,46 @@ def test_cabi_argument_errors_are_reported():
     assert rc == -1 and b"conv wgrad: fused prologue needs C % 32 == 0 and K % 4 == 0 (C=64, K=66)" in lib.dpft_last_error()
 
 
+def test_bn_pass_entries_refuse_what_their_workers_refuse():
+    """The storage-typed BatchNorm pass entries (dpft_*_any_f32, dpft_bn_act_sums_f32, dpft_cvt_f32_bf16): DPFT_ERR_ARG before
+    anything is launched, so testable without a GPU (the pointers are never read)."""
+    import ctypes as C
+    from dpft_amd.hip.lib import lib
+    p = [C.c_void_p(4096 * (i + 1)) for i in range(12)]
+    err = lambda: lib.dpft_last_error()
+    assert lib.dpft_bn_act_any_f32(p[0], p[1], None, None, 1, p[2], None, None, 8, 6, 0, None) == -1 and b"bn_act: bad arguments (K=6)" in err()
+    assert lib.dpft_bn_act_any_f32(p[0], p[1], None, p[3], 1, p[2], None, None, 8, 8, 1, None) == -1 and b"res_bnp without res" in err()
+    assert lib.dpft_bn_act_any_f32(p[0], p[1], None, None, 1, p[2], None, None, 8, 8, 2, None) == -1 and b"storage" in err()
+    assert lib.dpft_bn_act_any_f32(None, p[1], None, None, 1, p[2], None, None, 8, 8, 0, None) == -1
+    assert lib.dpft_bn_act_any_f32(C.c_void_p(4100), p[1], None, None, 1, p[2], None, None, 8, 8, 1, None) == -1 and b"aligned" in err()
+    used = C.c_int32(7)
+    a = (p[0], p[1], p[2], p[3], p[4], None, p[5])
+    assert lib.dpft_bn_act_sums_f32(*a, None, None, None, 0.0, 1, p[6], None, 8, 8, C.byref(used), None) == -1 and used.value == 0
+    assert b"without a residual" in err()
+    assert lib.dpft_bn_act_sums_f32(p[0], None, p[2], None, p[4], None, None, None, None, None, 0.0, 1, p[6], None, 8, 8,
+                                    C.byref(used), None) == -1 and b"without gamma" in err()
+    assert lib.dpft_bn_act_sums_f32(p[0], None, None, None, None, None, None, None, None, None, 0.0, 1, p[6], None, 8, 8,
+                                    C.byref(used), None) == -1
+    assert lib.dpft_bn_act_sums_f32(*a[:5], None, None, None, None, None, 0.0, 1, p[6], None, 8, 10, C.byref(used), None) == -1
+    assert lib.dpft_bn_bwd_reduce_any_f32(p[0], p[1], None, None, None, p[2], p[3], 8, 6, 0, None) == -1 and b"bn_bwd_reduce" in err()
+    assert lib.dpft_bn_bwd_reduce_any_f32(p[0], None, None, None, None, p[2], p[3], 8, 8, 1, None) == -1
+    ap = lambda **kw: lib.dpft_bn_bwd_apply_any_f32(p[0], p[1], None, None, None, p[2], p[3], p[4], p[5], None, None, kw.get("zb"),
+                                                    kw.get("zn", 0), 8, kw.get("K", 8), kw.get("st", 0), 0, None)
+    assert ap(K=6) == -1 and b"bn_bwd_apply" in err()
+    assert ap(zn=4) == -1 and b"zero_buf" in err()
+    assert ap(zb=p[4], zn=4) == -1 and b"must not be the sums" in err()
+    assert ap(st=3) == -1
+    assert lib.dpft_bn_relu_maxpool_any_f32(p[0], p[1], p[2], 1, 4, 4, 6, 2, 2, 0, None) == -1
+    assert lib.dpft_bn_relu_maxpool_any_f32(p[0], p[1], p[2], 1, 4, 4, 8, 3, 2, 1, None) == -1 and b"PH/PW inconsistent" in err()
+    assert lib.dpft_bn_relu_maxpool_bwd_any_f32(p[0], p[1], p[2], p[3], 1, 4, 4, 4, 3, 2, 0, None) == -1 and b"PH/PW inconsistent" in err()
+    assert lib.dpft_bn_relu_maxpool_bwd_any_f32(p[0], p[1], p[2], p[3], 1, 4, 4, 6, 2, 2, 0, None) == -1
+    assert lib.dpft_add_inplace_any_f32(p[0], p[1], 6, 1, None) == -1 and b"add_inplace" in err()
+    assert lib.dpft_cvt_f32_bf16(p[0], p[1], 6, None) == -1 and lib.dpft_cvt_f32_bf16(None, p[1], 8, None) == -1
+    assert lib.dpft_bn_last_form(None) == -1
+    form = C.c_int32(-1)
+    assert lib.dpft_bn_last_form(C.byref(form)) == 0 and form.value == 0          # nothing launched in this process
+
+
 def test_every_compute_entry_rejects_null_arguments():
     """Error behaviour of the boundary: every compute entry validates its arguments before touching the device and
     reports DPFT_ERR_ARG + a message through dpft_last_error() (no GPU needed; run in a child process because a missing
