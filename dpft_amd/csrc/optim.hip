@@ -5,6 +5,14 @@
 
 namespace dpft {
 
+// The 16-byte record the clip-coefficient launch writes and the clipped AdamW launch reads (include/dpft_hip.h).
+struct ClipRecord {
+    float norm;               // global L2 norm of the active gradients, before clipping
+    float coef;               // min(1, max_norm / (norm + 1e-6)); -1 = sit this step out (non-finite norm, "skip" mode)
+    int32_t nonfinite;        // this step's sum of squares was not finite
+    int32_t nonfinite_total;  // steps skipped for that reason so far ("skip" mode)
+};
+
 struct AdamChunk {
     float* p;
     const float* g;
@@ -20,12 +28,24 @@ struct AdamChunk {
 // `gate` (round 5, may be null): the step's loss on the device.  The reference steps only `if loss > 0` (training/trainer.py:131);
 // the trainer launches backward and optimizer without reading the loss back, and a loss that is not positive closes the gate
 // here: every tensor sits the step out exactly as if it had no gradient.
+// `CLIP` (dpft_adamw_clip_f32): every gradient element enters the update as g * clip->coef, the coefficient the two norm launches
+// below left in the clip record.  The product lives in registers only: the gradient in memory stays unclipped.  coef == 1.0f is
+// the unclipped update to the bit (g * 1.0f == g; contracted into an fma the product is exact either way).  A record that asks
+// for the step to be skipped (coef < 0: a non-finite norm in "skip" mode) closes the launch exactly as a gate that is not
+// positive does.  CLIP = false is the arithmetic of before.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void adamw_kernel(const AdamChunk* __restrict__ chunks, const int32_t* __restrict__ active,
                                                      int32_t* __restrict__ skipped, int32_t step,
                                                      float lr, float beta1, float beta2, float eps, float decay,
-                                                     float step_size, float inv_sqrt_bc2, const float* __restrict__ gate) {
+                                                     float step_size, float inv_sqrt_bc2, const float* __restrict__ gate,
+                                                     const ClipRecord* __restrict__ clip) {
     const AdamChunk c = chunks[blockIdx.x];
-    const bool closed = gate != nullptr && !(gate[0] > 0.f);
+    float coef = 1.f;
+    bool closed = gate != nullptr && !(gate[0] > 0.f);
+    if (CLIP) {
+        coef = clip->coef;
+        closed = closed || coef < 0.f;
+    }
     if (closed || (active && !active[c.tensor])) {             // parameters without a gradient are skipped (grad is None)
         if (skipped && c.m == nullptr && threadIdx.x == 0) skipped[c.tensor] += 1;   // marker row: one per tensor
         return;
@@ -42,7 +62,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamChunk* __restrict_
     for (int i = threadIdx.x * 4; i < c.n; i += 256 * 4) {
         if (i + 3 < c.n && ((((uintptr_t)(c.p + i)) | ((uintptr_t)(c.g + i))) & 15) == 0) {
             f32x4 p = *reinterpret_cast<f32x4*>(c.p + i);
-            const f32x4 g = *reinterpret_cast<const f32x4*>(c.g + i);
+            f32x4 g = *reinterpret_cast<const f32x4*>(c.g + i);
+            if (CLIP) g *= coef;
             f32x4 m = *reinterpret_cast<f32x4*>(c.m + i);
             f32x4 v = *reinterpret_cast<f32x4*>(c.v + i);
 #pragma unroll
@@ -59,13 +80,83 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamChunk* __restrict_
         } else {
             for (int e = i; e < min(i + 4, c.n); ++e) {
                 float p = c.p[e] * decay;
-                const float g = c.g[e];
+                const float g = CLIP ? c.g[e] * coef : c.g[e];
                 const float m = c.m[e] + (g - c.m[e]) * (1.f - beta1);
                 const float v = c.v[e] * beta2 + (1.f - beta2) * g * g;
                 p -= step_size * (m / (sqrtf(v) * inv_sqrt_bc2 + eps));
                 c.p[e] = p; c.m[e] = m; c.v[e] = v;
             }
         }
+    }
+}
+
+// Sum over a workgroup of 256 threads in a fixed order: the lanes of a wave by halving strides, then the four waves one after
+// the other through LDS.  The value is valid in thread 0.
+__device__ __forceinline__ double block_sum_256(double acc, double* wave_sums) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) wave_sums[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    return ((wave_sums[0] + wave_sums[1]) + wave_sums[2]) + wave_sums[3];
+}
+
+// Gradient clipping by global L2 norm, stage 1: partials[row] = sum of g^2 over the elements of chunk row `row`, one workgroup per
+// row of the table adamw_kernel reads, with its `active` flags.  Every element is widened to double BEFORE it is squared: the
+// product of two fp32 values is exact in fp64, so 3e19 does not overflow and 1e-30 does not flush, and a kernel that streams 4
+// bytes per element is nowhere near the fp64 rate.  16-byte loads where g + i is 16-byte aligned, scalar loads otherwise (the
+// split of adamw_kernel).  No atomics: each row has its own slot, a marker row and a row of an inactive tensor write 0.0, so
+// the partials -- and everything derived from them -- do not depend on which workgroup finishes when.
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const AdamChunk* __restrict__ chunks, const int32_t* __restrict__ active,
+                                                           double* __restrict__ partials) {
+    __shared__ double wave_sums[4];
+    const AdamChunk c = chunks[blockIdx.x];
+    if (c.m == nullptr || c.n <= 0 || (active && !active[c.tensor])) {      // (uniform over the workgroup)
+        if (threadIdx.x == 0) partials[blockIdx.x] = 0.0;
+        return;
+    }
+    double acc = 0.0;
+    for (int i = threadIdx.x * 4; i < c.n; i += 256 * 4) {
+        if (i + 3 < c.n && (((uintptr_t)(c.g + i)) & 15) == 0) {
+            const f32x4 g = *reinterpret_cast<const f32x4*>(c.g + i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const double d = (double)g[e];
+                acc += d * d;
+            }
+        } else {
+            for (int e = i; e < min(i + 4, c.n); ++e) {
+                const double d = (double)c.g[e];
+                acc += d * d;
+            }
+        }
+    }
+    acc = block_sum_256(acc, wave_sums);
+    if (threadIdx.x == 0) partials[blockIdx.x] = acc;
+}
+
+// Stage 2, ONE workgroup: S = sum of partials[0 .. n) -- thread t adds partials[t], partials[t + 256], ... in index order, then
+// the fixed tree of block_sum_256: the same bits from run to run -- and the clip record.  norm = (float)sqrt(S); coef is
+// torch.nn.utils.clip_grad_norm_'s rule (norm_type 2, error_if_nonfinite=False) evaluated in fp64 and rounded once.  S not
+// finite: mode 0 ("propagate") leaves coef to the formula (NaN for a NaN norm, 0 for an infinite one: what torch multiplies the
+// gradients by), mode 1 ("skip") writes coef = -1, which closes the clipped AdamW launch, and counts the step.
+__global__ __launch_bounds__(256) void grad_clip_coef_kernel(const double* __restrict__ partials, int32_t n, double max_norm,
+                                                              int32_t nonfinite_mode, ClipRecord* __restrict__ record) {
+    __shared__ double wave_sums[4];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) acc += partials[i];
+    const double S = block_sum_256(acc, wave_sums);
+    if (threadIdx.x == 0) {
+        const double norm = sqrt(S);
+        const bool bad = !isfinite(S);
+        const double r = max_norm / (norm + 1e-6);
+        float coef = (float)(r >= 1.0 ? 1.0 : r);      // (a NaN compares false and passes through, as through torch's clamp)
+        if (bad && nonfinite_mode == 1) {
+            coef = -1.f;
+            record->nonfinite_total += 1;
+        }
+        record->norm = (float)norm;
+        record->coef = coef;
+        record->nonfinite = bad ? 1 : 0;
     }
 }
 
@@ -78,7 +169,36 @@ extern "C" int dpft_adamw_f32(const void* chunks, int32_t n_chunks, const int32_
                               dpft_stream_t stream) {
     DPFT_REQUIRE(chunks && n_chunks > 0 && step >= 1, "adamw: bad arguments");
     const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    hipLaunchKernelGGL(adamw_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const AdamChunk*)chunks, active, skipped, step, lr,
-                       beta1, beta2, eps, (float)(1.0 - (double)lr * weight_decay), (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), gate);
+    hipLaunchKernelGGL(adamw_kernel<false>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const AdamChunk*)chunks, active, skipped,
+                       step, lr, beta1, beta2, eps, (float)(1.0 - (double)lr * weight_decay), (float)(lr / bc1),
+                       (float)(1.0 / sqrt(bc2)), gate, (const ClipRecord*)nullptr);
     return check_launch("adamw");
+}
+
+extern "C" int dpft_adamw_clip_f32(const void* chunks, int32_t n_chunks, const int32_t* active, int32_t* skipped, float lr,
+                                   float beta1, float beta2, float eps, float weight_decay, int32_t step, const float* gate,
+                                   const void* record, dpft_stream_t stream) {
+    DPFT_REQUIRE(chunks && n_chunks > 0 && step >= 1 && record, "adamw_clip: bad arguments");
+    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+    hipLaunchKernelGGL(adamw_kernel<true>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const AdamChunk*)chunks, active, skipped,
+                       step, lr, beta1, beta2, eps, (float)(1.0 - (double)lr * weight_decay), (float)(lr / bc1),
+                       (float)(1.0 / sqrt(bc2)), gate, (const ClipRecord*)record);
+    return check_launch("adamw_clip");
+}
+
+extern "C" int dpft_grad_sqnorm_f32(const void* chunks, int32_t n_chunks, const int32_t* active, double* partials,
+                                    dpft_stream_t stream) {
+    DPFT_REQUIRE(chunks && n_chunks > 0 && partials, "grad_sqnorm: bad arguments");
+    hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const AdamChunk*)chunks, active, partials);
+    return check_launch("grad_sqnorm");
+}
+
+extern "C" int dpft_grad_clip_coef_f32(const double* partials, int32_t n_partials, float max_norm, int32_t nonfinite_mode,
+                                       void* record, dpft_stream_t stream) {
+    DPFT_REQUIRE(partials && n_partials > 0 && record, "grad_clip_coef: bad arguments");
+    DPFT_REQUIRE(max_norm > 0.f && max_norm <= 3.402823466e38f, "grad_clip_coef: max_norm %g is not finite and positive", (double)max_norm);
+    DPFT_REQUIRE(nonfinite_mode == 0 || nonfinite_mode == 1, "grad_clip_coef: nonfinite_mode %d (0 propagate | 1 skip)", nonfinite_mode);
+    hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n_partials, (double)max_norm,
+                       nonfinite_mode, (ClipRecord*)record);
+    return check_launch("grad_clip_coef");
 }

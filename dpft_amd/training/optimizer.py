@@ -31,6 +31,65 @@ class FusedAdamW(torch.optim.Optimizer):
         self._segments = None          # list of lists of parameters (a parameter not listed belongs to the trailing segment)
         self._round_open = False       # a step_segment() of the current step has already advanced _step
         self._done = set()             # (table index, segment index) launched in the current step
+        # Clipping by global L2 norm (set_clip): off unless asked for.  _partials = one double per chunk-table row of every
+        # group, _clip_record = the 16 bytes {norm, coef, nonfinite, nonfinite_total} the norm launches leave for the AdamW launch.
+        self._clip = None              # (max_norm, nonfinite mode 0 | 1)
+        self._partials = None
+        self._clip_record = None
+
+    NONFINITE_MODES = {"propagate": 0, "skip": 1}
+
+    def set_clip(self, max_norm, nonfinite: str = "propagate"):
+        """Clip the gradients by their global L2 norm inside step(), on the device: ``torch.nn.utils.clip_grad_norm_(params,
+        max_norm)`` (norm_type 2, error_if_nonfinite=False) followed by the AdamW update, without a host read-back and without
+        touching the gradients -- the update uses ``g * coef`` in registers, ``.grad`` KEEPS THE UNCLIPPED gradient.  The norm
+        covers the parameters that take part in the step (a gradient this step, active, gate open or not).  ``max_norm=None``
+        switches clipping off.  ``nonfinite``: what a NaN / infinite norm does -- "propagate" (torch: the coefficient is NaN or 0
+        and the parameters follow) or "skip" (the step is dropped exactly like a closed gate: nothing moves, the per-parameter
+        step counts do not advance, nonfinite_steps() counts it)."""
+        assert not self._round_open, "FusedAdamW.set_clip between step_segment() and step()"
+        if max_norm is None:
+            self._clip = None
+            return
+        if nonfinite not in self.NONFINITE_MODES:
+            raise ValueError(f"nonfinite must be 'propagate' or 'skip', not {nonfinite!r}")
+        if isinstance(max_norm, bool) or not isinstance(max_norm, (int, float)) or not (0.0 < float(max_norm) < float("inf")):
+            raise ValueError(f"max_norm must be a finite positive number, not {max_norm!r}")
+        self._clip = (float(max_norm), self.NONFINITE_MODES[nonfinite])
+        if self._clip_record is None:      # allocated once: nonfinite_total lives in it
+            dev = next(p for g in self.param_groups for p in g["params"]).device
+            self._clip_record = torch.zeros(4, dtype=torch.int32, device=dev)
+
+    def last_grad_norm(self):
+        """The global gradient norm of the last clipped step BEFORE clipping (what clip_grad_norm_ returns): a device scalar
+        that views the clip record -- no synchronisation, the next step overwrites it.  None when clipping was never on."""
+        return None if self._clip_record is None else self._clip_record.view(torch.float32)[0]
+
+    def nonfinite_steps(self) -> int:
+        """Steps whose gradient norm was not finite in "skip" mode.  Reads the counter back (synchronises).  The norm launches
+        do not see the `loss > 0` gate, so a step that the gate closed anyway is counted too when its gradients were not finite
+        (a NaN loss does both: it closes the gate and makes the gradients NaN); last_grad_norm() of such a step is NaN as well."""
+        return 0 if self._clip_record is None else int(self._clip_record[3])
+
+    def grad_sqnorms(self):
+        """Per-tensor squared gradient norms of the last clipped step, fp64, one device tensor per parameter group with one
+        entry per trainable parameter (0 for a tensor that sat the step out).  Computed on demand from the per-row partial
+        sums; not on the step path."""
+        assert self._partials is not None and self._tables is not None, "grad_sqnorms() needs a step() with clipping on"
+        out = []
+        for t in self._tables:
+            idx = torch.from_numpy(t["row_tensor"]).to(self._partials.device)
+            part = self._partials[t["part_off"]:t["part_off"] + t["n_chunks"]]
+            out.append(torch.zeros(len(t["params"]), dtype=torch.float64, device=part.device).index_add_(0, idx, part))
+        return out
+
+    def _size_partials(self):
+        """One double per row of every group's table; each table owns the range starting at its part_off."""
+        total = 0
+        for t in self._tables:
+            t["part_off"] = total
+            total += t["n_chunks"]
+        self._partials = torch.zeros(total, dtype=torch.float64, device=self._tables[0]["chunks"].device)
 
     def attach_segments(self, param_lists):
         """Declare the segments (lists of parameters, e.g. GradBucketReducer buckets) step_segment() may be called with."""
@@ -136,9 +195,12 @@ class FusedAdamW(torch.optim.Optimizer):
             active = torch.ones(len(ps), dtype=torch.int32, device=dev)
             tables.append(dict(params=ps, ptrs=self._ptrs(ps), m=m, v=v, skipped=skipped, chunks=chunks,
                                n_chunks=len(rows), active=active, active_host=None, seg_range=seg_range,
-                               seg_tensors=seg_tensors))
+                               seg_tensors=seg_tensors, row_tensor=arr["t"].astype(np.int64)))
         self._tables = tables
         self._restore = False
+        self._partials = None
+        if self._clip is not None:
+            self._size_partials()
 
     def set_gate(self, loss: "torch.Tensor" = None):
         """Device-side `if loss > 0` (trainer.py:131) for the NEXT step(): a scalar tensor that stays on the device; the launch
@@ -156,10 +218,25 @@ class FusedAdamW(torch.optim.Optimizer):
             return
         b1, b2 = group["betas"]
         import ctypes as C
-        lib.call("dpft_adamw_f32", C.c_void_p(t["chunks"].data_ptr() + first * self.CHUNK_BYTES), count, ptr(t["active"]),
-                 ptr(t["skipped"]),
-                 float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
-                 self._step, ptr(getattr(self, "_gate", None)), stream())
+        args = (C.c_void_p(t["chunks"].data_ptr() + first * self.CHUNK_BYTES), count, ptr(t["active"]), ptr(t["skipped"]),
+                float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
+                self._step, ptr(getattr(self, "_gate", None)))
+        if self._clip is not None:
+            lib.call("dpft_adamw_clip_f32", *args, ptr(self._clip_record), stream())
+        else:
+            lib.call("dpft_adamw_f32", *args, stream())
+
+    def _launch_norm(self):
+        """The two norm launches of a clipped step: the sum of squares of every group's table into its range of the partials,
+        then one workgroup that adds the partials up and writes the clip record."""
+        import ctypes as C
+        if self._partials is None:
+            self._size_partials()
+        for t in self._tables:
+            lib.call("dpft_grad_sqnorm_f32", ptr(t["chunks"]), t["n_chunks"], ptr(t["active"]),
+                     C.c_void_p(self._partials.data_ptr() + 8 * t["part_off"]), stream())
+        lib.call("dpft_grad_clip_coef_f32", ptr(self._partials), self._partials.numel(), self._clip[0], self._clip[1],
+                 ptr(self._clip_record), stream())
 
     @torch.no_grad()
     def step_segment(self, si: int) -> bool:
@@ -168,6 +245,8 @@ class FusedAdamW(torch.optim.Optimizer):
         step out (its `active` flag on the device would have to change first).  The step count advances once per step."""
         if self._segments is None or self._restore or self._tables is None:
             return False
+        if self._clip is not None:
+            return False      # the coefficient needs the norm over ALL buckets: no bucket can be stepped before step()
         if getattr(self, "gate_required", False) and getattr(self, "_gate", None) is None:
             return False      # the step's `loss > 0` decision is taken on the device: never launch ahead of its gate
         if any(self._ptrs(t["params"]) != t["ptrs"] for t in self._tables):
@@ -203,6 +282,9 @@ class FusedAdamW(torch.optim.Optimizer):
                 # (tensors of segments already stepped in this round were all active, before and now: their flags do not move)
                 t["active"].copy_(torch.tensor(host, dtype=torch.int32))
                 t["active_host"] = host
+        if self._clip is not None:
+            self._launch_norm()
+        for gi, (group, t) in enumerate(zip(self.param_groups, self._tables)):
             if not any(g == gi for g, _ in self._done):
                 self._launch(group, t, 0, t["n_chunks"])                # nothing stepped early: the one launch of before
             else:

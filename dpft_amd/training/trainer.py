@@ -53,6 +53,22 @@ class _ScalarLog:
             self._fh.close()
 
 
+def parse_clip_grad_norm(value):
+    """``train.clip_grad_norm`` -> (max_norm, nonfinite): a positive finite number, or ``{"max_norm": x, "nonfinite":
+    "propagate" | "skip"}`` ("propagate", torch's behaviour, when left out).  Anything else is a ValueError."""
+    nonfinite = "propagate"
+    if isinstance(value, dict):
+        if "max_norm" not in value or set(value) - {"max_norm", "nonfinite"}:
+            raise ValueError(f"train.clip_grad_norm: expected {{'max_norm': x, 'nonfinite': ...}}, got {value!r}")
+        nonfinite = value.get("nonfinite", "propagate")
+        value = value["max_norm"]
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not (0.0 < float(value) < float("inf")):
+        raise ValueError(f"train.clip_grad_norm: max_norm must be a finite positive number, got {value!r}")
+    if nonfinite not in ("propagate", "skip"):
+        raise ValueError(f"train.clip_grad_norm: nonfinite must be 'propagate' or 'skip', got {nonfinite!r}")
+    return float(value), nonfinite
+
+
 class DataParallelTrainer:
     def __init__(self, model: torch.nn.Module, config: Dict[str, Any], device, bucket_mb: Optional[float] = None,
                  comm_dtype: Optional[str] = None, force_collectives: bool = False):
@@ -135,6 +151,20 @@ class DataParallelTrainer:
         # the exposed tail of the exchange; off by default.
         self.early_adamw = (isinstance(self.optimizer, FusedAdamW) and self.device.type == "cuda"
                             and os.environ.get("DPFT_EARLY_ADAMW", "0") == "1")
+        # Optional extension (the reference does not clip): train.clip_grad_norm = x | {"max_norm": x, "nonfinite": ...} clips the
+        # gradients by their global L2 norm before the update.  FusedAdamW does it on the device inside step() (two norm launches,
+        # no read-back, .grad stays unclipped); any other optimizer gets torch.nn.utils.clip_grad_norm_ between reducer.finish()
+        # and optimizer.step().  The norm is taken after finish(), on gradients every rank holds identically: no new collective.
+        self.clip = parse_clip_grad_norm(train["clip_grad_norm"]) if "clip_grad_norm" in train else None
+        self.last_grad_norm = None                         # with the key set: the last step's norm before clipping (a device scalar)
+        self._nonfinite_eager = 0                          # eager path, "skip": steps dropped for a non-finite norm
+        if self.clip is not None:
+            self.last_grad_norm = torch.zeros((), device=device)
+            if isinstance(self.optimizer, FusedAdamW):
+                self.optimizer.set_clip(*self.clip)
+                # no bucket can be stepped before the norm over all buckets is known (step_segment() would refuse every call):
+                # early AdamW stays off even with DPFT_EARLY_ADAMW=1
+                self.early_adamw = False
         if self.early_adamw:
             self.optimizer.attach_segments([b["params"] for b in self.reducer.buckets])
             self.reducer.on_bucket_final = self.optimizer.step_segment
@@ -238,7 +268,20 @@ class DataParallelTrainer:
             self.reducer.finish()
             if isinstance(self.optimizer, FusedAdamW):
                 self.optimizer.set_active(self.reducer.seen_ids())
-            self.optimizer.step()
+            dropped = False
+            if self.clip is not None and not isinstance(self.optimizer, FusedAdamW):
+                # eager path: torch clips the final gradients in place (here .grad ends up clipped, unlike the fused path)
+                grads = [p for p in self.model.parameters() if p.grad is not None]
+                self.last_grad_norm = torch.nn.utils.clip_grad_norm_(grads, self.clip[0]).detach()
+                if self.clip[1] == "skip" and not bool(torch.isfinite(self.last_grad_norm)):
+                    dropped = True
+                    self._nonfinite_eager += 1
+            if not dropped:
+                self.optimizer.step()
+            if self.clip is not None and isinstance(self.optimizer, FusedAdamW):
+                self.last_grad_norm = self.optimizer.last_grad_norm()      # a view of the clip record: the next step overwrites it
+        elif self.clip is not None:
+            self.last_grad_norm = torch.zeros((), device=self.device)
         if hasattr(self.loss_fn, "__dict__"):
             # validation calls the same loss_fn: without this every eval batch would launch the criterion's gradient kernel
             # into the decoder graph's static gradient buffers
@@ -246,6 +289,13 @@ class DataParallelTrainer:
         if with_metrics and self.eval_fn is not None:
             return loss.detach(), {k: v.detach() for k, v in losses.items()}, self.eval_fn(output, labels)
         return loss.detach(), {k: v.detach() for k, v in losses.items()}
+
+    def nonfinite_steps(self) -> int:
+        """Steps whose gradient norm was not finite under ``"nonfinite": "skip"``: FusedAdamW's device counter (read back on
+        demand; see FusedAdamW.nonfinite_steps for steps the loss gate closed as well), the eager path's own count otherwise."""
+        if isinstance(self.optimizer, FusedAdamW):
+            return self.optimizer.nonfinite_steps()
+        return self._nonfinite_eager
 
     def _backward_without_engine(self, loss: torch.Tensor) -> bool:
         """Replayed decoder + fused loss: their two backward steps are launched directly (GraphedFuser.backward_from),
@@ -379,6 +429,8 @@ class DataParallelTrainer:
             scalars = {f"loss_{k}": v for k, v in losses.items()}
             scalars["loss"] = loss
             scalars.update(metrics)
+            if self.clip is not None:                      # only with train.clip_grad_norm set: default runs log what they always did
+                scalars["grad_norm"] = self.last_grad_norm
             if self.logging == "step":
                 self._log(writer if self.rank == 0 else None, self._rank_mean(scalars), step, "train")
             for k, v in scalars.items():

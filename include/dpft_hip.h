@@ -781,6 +781,38 @@ int dpft_adamw_f32(const void* chunks, int32_t n_chunks, const int32_t* active, 
                    float beta2, float eps, float weight_decay, int32_t step, const float* gate, dpft_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Gradient clipping by global L2 norm on the device (torch.nn.utils.clip_grad_norm_, norm_type 2,
+ * error_if_nonfinite=False), an extension: the reference does not clip.  Three launches, no host read-back:
+ *
+ * dpft_grad_sqnorm_f32: partials[r] = sum of g^2 over chunk row r of the table dpft_adamw_f32 reads (same `chunks`, same
+ * `active`), one workgroup per row.  Every element is widened to double before it is squared (an fp32 square is exact in
+ * fp64: no overflow at 3e19, no flush at 1e-30) and summed in double in a fixed order.  A marker row and a row of an
+ * inactive tensor write 0.0.  No atomics: the partials are the same bits from run to run.  Several tables (parameter
+ * groups) write disjoint ranges of one `partials` buffer.
+ *
+ * dpft_grad_clip_coef_f32: ONE workgroup sums partials[0 .. n_partials) in a fixed order to S and writes the 16-byte clip
+ * record {float norm; float coef; int32 nonfinite; int32 nonfinite_total}: norm = (float)sqrt(S) (the norm BEFORE
+ * clipping, as torch returns it), coef = (float)min(1, max_norm / (sqrt(S) + 1e-6)) evaluated in fp64 and rounded once.
+ * max_norm must be finite and positive; it crosses the boundary as a float, so the coefficient is that of the fp32-rounded
+ * max_norm (0.1 -> 0.100000001490116: 1.5e-8 relative, a fraction of the coefficient's own fp32 rounding).  S not finite: nonfinite = 1 (else 0) and, by nonfinite_mode,
+ *   0 "propagate" (torch's behaviour): coef is what the formula gives -- NaN for a NaN norm, 0 for an infinite one;
+ *   1 "skip": coef = -1, which tells dpft_adamw_clip_f32 to sit the step out, and nonfinite_total += 1.
+ * nonfinite_total is only ever incremented: the caller zeroes the record once, when it allocates it.
+ *
+ * dpft_adamw_clip_f32: dpft_adamw_f32 with every gradient element replaced by g * record->coef in registers.  Nothing
+ * is written back to the gradients: they stay unclipped in memory.  coef == 1 gives the results of dpft_adamw_f32 to the
+ * bit.  coef < 0 closes the launch exactly as a gate that is not positive does: no parameter or moment moves and
+ * skipped[t] advances for every tensor.
+ * ---------------------------------------------------------------------------------------- */
+int dpft_grad_sqnorm_f32(const void* chunks, int32_t n_chunks, const int32_t* active, double* partials,
+                         dpft_stream_t stream);
+int dpft_grad_clip_coef_f32(const double* partials, int32_t n_partials, float max_norm, int32_t nonfinite_mode,
+                            void* record, dpft_stream_t stream);
+int dpft_adamw_clip_f32(const void* chunks, int32_t n_chunks, const int32_t* active, int32_t* skipped, float lr,
+                        float beta1, float beta2, float eps, float weight_decay, int32_t step, const float* gate,
+                        const void* record, dpft_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline`): while started, every dpft_conv2d_nhwc_* call is bracketed
  * by HIP events on its launch stream.  Not thread-safe; do not use inside a graph capture.
  * ---------------------------------------------------------------------------------------- */
