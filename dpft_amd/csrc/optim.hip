@@ -33,12 +33,21 @@ struct AdamChunk {
 // the unclipped update to the bit (g * 1.0f == g; contracted into an fma the product is exact either way).  A record that asks
 // for the step to be skipped (coef < 0: a non-finite norm in "skip" mode) closes the launch exactly as a gate that is not
 // positive does.  CLIP = false is the arithmetic of before.
-template <bool CLIP>
+// `EMA` (dpft_adamw_ema_f32): an exponential moving average of the weights, kept in a third flat buffer laid out like the
+// moments: the chunk's slice is ema_base + (c.m - m_base), so AdamChunk stays 40 bytes and `ema` has the alignment of `m`.  The
+// new p is still in registers when ema += (p - ema) * w is formed (ema.lerp_(p, 1 - d), the rule of
+// torch.optim.swa_utils.get_ema_multi_avg_fn): one more read-modify-write per element, no second pass over the weights.
+// w = (float)(1 - d_eff), d_eff in double: the configured decay, or with warm-up min(decay, (1 + own) / (10 + own)) with `own`
+// the tensor's OWN step count, the one the bias corrections use.  Every block that returns early (closed gate, coef < 0,
+// inactive tensor, marker row) returns before it: the average of a tensor advances exactly when the tensor is updated.  p, m
+// and v do not depend on it.  EMA = false is the code of before (the four trailing arguments are not read).
+template <bool CLIP, bool EMA>
 __global__ __launch_bounds__(256) void adamw_kernel(const AdamChunk* __restrict__ chunks, const int32_t* __restrict__ active,
                                                      int32_t* __restrict__ skipped, int32_t step,
                                                      float lr, float beta1, float beta2, float eps, float decay,
                                                      float step_size, float inv_sqrt_bc2, const float* __restrict__ gate,
-                                                     const ClipRecord* __restrict__ clip) {
+                                                     const ClipRecord* __restrict__ clip, const float* m_base, float* ema_base,
+                                                     float ema_decay, int32_t ema_warmup) {
     const AdamChunk c = chunks[blockIdx.x];
     float coef = 1.f;
     bool closed = gate != nullptr && !(gate[0] > 0.f);
@@ -51,13 +60,22 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamChunk* __restrict_
         return;
     }
     if (c.m == nullptr) return;                    // marker row of an active tensor
+    int32_t own = step;
     if (skipped) {
-        const int32_t own = step - skipped[c.tensor];
+        own = step - skipped[c.tensor];
         if (own != step) {                         // bias corrections of this tensor's own step count
             const double bc1 = 1.0 - pow((double)beta1, (double)own), bc2 = 1.0 - pow((double)beta2, (double)own);
             step_size = (float)((double)lr / bc1);
             inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
         }
+    }
+    float* ema = nullptr;
+    float w = 0.f;
+    if (EMA) {
+        ema = ema_base + (c.m - m_base);
+        double d_eff = (double)ema_decay;
+        if (ema_warmup) d_eff = fmin(d_eff, (1.0 + (double)own) / (10.0 + (double)own));
+        w = (float)(1.0 - d_eff);
     }
     for (int i = threadIdx.x * 4; i < c.n; i += 256 * 4) {
         if (i + 3 < c.n && ((((uintptr_t)(c.p + i)) | ((uintptr_t)(c.g + i))) & 15) == 0) {
@@ -66,6 +84,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamChunk* __restrict_
             if (CLIP) g *= coef;
             f32x4 m = *reinterpret_cast<f32x4*>(c.m + i);
             f32x4 v = *reinterpret_cast<f32x4*>(c.v + i);
+            f32x4 a;
+            if (EMA) a = *reinterpret_cast<f32x4*>(ema + i);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 p[e] *= decay;
@@ -73,7 +93,9 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamChunk* __restrict_
                 v[e] = v[e] * beta2 + (1.f - beta2) * g[e] * g[e];
                 const float denom = sqrtf(v[e]) * inv_sqrt_bc2 + eps;
                 p[e] -= step_size * (m[e] / denom);
+                if (EMA) a[e] = a[e] + (p[e] - a[e]) * w;                   // ema.lerp_(p, 1 - d)
             }
+            if (EMA) *reinterpret_cast<f32x4*>(ema + i) = a;
             *reinterpret_cast<f32x4*>(c.p + i) = p;
             *reinterpret_cast<f32x4*>(c.m + i) = m;
             *reinterpret_cast<f32x4*>(c.v + i) = v;
@@ -84,6 +106,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamChunk* __restrict_
                 const float m = c.m[e] + (g - c.m[e]) * (1.f - beta1);
                 const float v = c.v[e] * beta2 + (1.f - beta2) * g * g;
                 p -= step_size * (m / (sqrtf(v) * inv_sqrt_bc2 + eps));
+                if (EMA) ema[e] = ema[e] + (p - ema[e]) * w;
                 c.p[e] = p; c.m[e] = m; c.v[e] = v;
             }
         }
@@ -160,6 +183,33 @@ __global__ __launch_bounds__(256) void grad_clip_coef_kernel(const double* __res
     }
 }
 
+// One row of dpft_swap_f32's table: two disjoint fp32 ranges of n elements that change places.
+struct SwapRow {
+    float* a;
+    float* b;
+    int32_t n;
+    int32_t pad;
+};
+
+// a[0 .. n) <-> b[0 .. n), one workgroup per row: 16-byte accesses where both pointers are 16-byte aligned and four elements
+// remain, scalar accesses otherwise (the split of adamw_kernel).  Each element is read and written by one thread only.
+__global__ __launch_bounds__(256) void swap_kernel(const SwapRow* __restrict__ rows) {
+    const SwapRow r = rows[blockIdx.x];
+    for (int i = threadIdx.x * 4; i < r.n; i += 256 * 4) {
+        if (i + 3 < r.n && ((((uintptr_t)(r.a + i)) | ((uintptr_t)(r.b + i))) & 15) == 0) {
+            const f32x4 a = *reinterpret_cast<const f32x4*>(r.a + i);
+            const f32x4 b = *reinterpret_cast<const f32x4*>(r.b + i);
+            *reinterpret_cast<f32x4*>(r.a + i) = b;
+            *reinterpret_cast<f32x4*>(r.b + i) = a;
+        } else {
+            for (int e = i; e < min(i + 4, r.n); ++e) {
+                const float a = r.a[e], b = r.b[e];
+                r.a[e] = b; r.b[e] = a;
+            }
+        }
+    }
+}
+
 }  // namespace dpft
 
 using namespace dpft;
@@ -169,9 +219,9 @@ extern "C" int dpft_adamw_f32(const void* chunks, int32_t n_chunks, const int32_
                               dpft_stream_t stream) {
     DPFT_REQUIRE(chunks && n_chunks > 0 && step >= 1, "adamw: bad arguments");
     const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    hipLaunchKernelGGL(adamw_kernel<false>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const AdamChunk*)chunks, active, skipped,
+    hipLaunchKernelGGL((adamw_kernel<false, false>), dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const AdamChunk*)chunks, active, skipped,
                        step, lr, beta1, beta2, eps, (float)(1.0 - (double)lr * weight_decay), (float)(lr / bc1),
-                       (float)(1.0 / sqrt(bc2)), gate, (const ClipRecord*)nullptr);
+                       (float)(1.0 / sqrt(bc2)), gate, (const ClipRecord*)nullptr, (const float*)nullptr, (float*)nullptr, 0.f, 0);
     return check_launch("adamw");
 }
 
@@ -180,10 +230,36 @@ extern "C" int dpft_adamw_clip_f32(const void* chunks, int32_t n_chunks, const i
                                    const void* record, dpft_stream_t stream) {
     DPFT_REQUIRE(chunks && n_chunks > 0 && step >= 1 && record, "adamw_clip: bad arguments");
     const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    hipLaunchKernelGGL(adamw_kernel<true>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const AdamChunk*)chunks, active, skipped,
+    hipLaunchKernelGGL((adamw_kernel<true, false>), dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const AdamChunk*)chunks, active, skipped,
                        step, lr, beta1, beta2, eps, (float)(1.0 - (double)lr * weight_decay), (float)(lr / bc1),
-                       (float)(1.0 / sqrt(bc2)), gate, (const ClipRecord*)record);
+                       (float)(1.0 / sqrt(bc2)), gate, (const ClipRecord*)record, (const float*)nullptr, (float*)nullptr, 0.f, 0);
     return check_launch("adamw_clip");
+}
+
+extern "C" int dpft_adamw_ema_f32(const void* chunks, int32_t n_chunks, const int32_t* active, int32_t* skipped, float lr,
+                                  float beta1, float beta2, float eps, float weight_decay, int32_t step, const float* gate,
+                                  const void* record, const float* m_base, float* ema_base, float ema_decay, int32_t ema_warmup,
+                                  dpft_stream_t stream) {
+    DPFT_REQUIRE(chunks && n_chunks > 0 && step >= 1 && m_base && ema_base, "adamw_ema: bad arguments");
+    DPFT_REQUIRE(ema_decay >= 0.f && ema_decay < 1.f, "adamw_ema: ema_decay %g is not in [0, 1)", (double)ema_decay);
+    DPFT_REQUIRE(ema_warmup == 0 || ema_warmup == 1, "adamw_ema: ema_warmup %d (0 off | 1 on)", ema_warmup);
+    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+    const float decay = (float)(1.0 - (double)lr * weight_decay), step_size = (float)(lr / bc1), inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    if (record)
+        hipLaunchKernelGGL((adamw_kernel<true, true>), dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const AdamChunk*)chunks,
+                           active, skipped, step, lr, beta1, beta2, eps, decay, step_size, inv_sqrt_bc2, gate,
+                           (const ClipRecord*)record, m_base, ema_base, ema_decay, ema_warmup);
+    else
+        hipLaunchKernelGGL((adamw_kernel<false, true>), dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const AdamChunk*)chunks,
+                           active, skipped, step, lr, beta1, beta2, eps, decay, step_size, inv_sqrt_bc2, gate,
+                           (const ClipRecord*)nullptr, m_base, ema_base, ema_decay, ema_warmup);
+    return check_launch("adamw_ema");
+}
+
+extern "C" int dpft_swap_f32(const void* rows, int32_t n_rows, dpft_stream_t stream) {
+    DPFT_REQUIRE(rows && n_rows > 0, "swap: bad arguments");
+    hipLaunchKernelGGL(swap_kernel, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, (const SwapRow*)rows);
+    return check_launch("swap");
 }
 
 extern "C" int dpft_grad_sqnorm_f32(const void* chunks, int32_t n_chunks, const int32_t* active, double* partials,

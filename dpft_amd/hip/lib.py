@@ -196,6 +196,8 @@ SIGNATURES = {
     "dpft_grad_sqnorm_f32": (_I, [_P, _I, _P, _P, _P]),
     "dpft_grad_clip_coef_f32": (_I, [_P, _I, _F, _I, _P, _P]),
     "dpft_adamw_clip_f32": (_I, [_P, _I, _P, _P, _F, _F, _F, _F, _F, _I, _P, _P, _P]),
+    "dpft_adamw_ema_f32": (_I, [_P, _I, _P, _P, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P, _F, _I, _P]),
+    "dpft_swap_f32": (_I, [_P, _I, _P]),
     "dpft_resnet_plan_create": (_L, [C.POINTER(ResnetDesc)]),
     "dpft_resnet_plan_destroy": (None, [_L]),
     "dpft_resnet_plan_query": (_L, [_L, _I, _I]),

@@ -12,6 +12,18 @@ from dpft_amd.hip.lib import lib, note_weights_changed, ptr, stream
 CHUNK = 16384
 
 
+def ema_decay_ok(decay) -> bool:
+    """A usable EMA decay: a real number (not a bool) that lies in [0, 1) AFTER rounding to fp32, the form in which it crosses
+    the C boundary (0.99999999 rounds to 1.0 and is refused).  Never raises: an int too large for a float is simply not usable."""
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)):
+        return False
+    try:
+        d = float(decay)
+    except OverflowError:
+        return False
+    return 0.0 <= d < 1.0 and float(np.float32(d)) < 1.0
+
+
 class FusedAdamW(torch.optim.Optimizer):
     """Drop-in for ``torch.optim.AdamW`` (no amsgrad / maximize / capturable).  The moments of a parameter group live in
     two flat fp32 buffers; ``self.state[p]`` holds views into them, so ``state_dict()`` / ``load_state_dict()`` round-trip
@@ -36,6 +48,8 @@ class FusedAdamW(torch.optim.Optimizer):
         self._clip = None              # (max_norm, nonfinite mode 0 | 1)
         self._partials = None
         self._clip_record = None
+        # EMA of the weights (set_ema): off unless asked for.  A third flat buffer per group, laid out like the moments.
+        self._ema = None               # (decay, warmup 0 | 1)
 
     NONFINITE_MODES = {"propagate": 0, "skip": 1}
 
@@ -59,6 +73,84 @@ class FusedAdamW(torch.optim.Optimizer):
         if self._clip_record is None:      # allocated once: nonfinite_total lives in it
             dev = next(p for g in self.param_groups for p in g["params"]).device
             self._clip_record = torch.zeros(4, dtype=torch.int32, device=dev)
+
+    def set_ema(self, decay, warmup: bool = False):
+        """Keep an exponential moving average of the weights inside step(): ``ema.lerp_(p, 1 - decay)`` on every element the
+        launch updates (the rule of ``torch.optim.swa_utils.get_ema_multi_avg_fn``), in a flat fp32 buffer per group laid out
+        like the moments and seeded with the current parameter values.  A tensor that sits a step out (no gradient, closed
+        gate, a step dropped by clipping's "skip" mode) keeps its average.  ``warmup``: the decay of a tensor's n-th own step is
+        ``min(decay, (1 + n) / (10 + n))``.  ``self.state[p]["ema"]`` views the buffer, so state_dict() / load_state_dict()
+        carry it.  ``decay=None`` switches the EMA off and drops the buffers."""
+        assert not self._round_open, "FusedAdamW.set_ema between step_segment() and step()"
+        if decay is None:
+            self._ema = None
+            for t in self._tables or []:
+                for k in ("ema", "swap", "n_swap"):
+                    t.pop(k, None)
+            for st in self.state.values():
+                st.pop("ema", None)
+            return
+        if not ema_decay_ok(decay):
+            raise ValueError(f"decay must be a number in [0, 1) (as a float32), not {decay!r}")
+        if not isinstance(warmup, (bool, np.bool_)):
+            raise ValueError(f"warmup must be a bool, not {warmup!r}")
+        self._ema = (float(decay), int(bool(warmup)))
+        if self._tables is not None and not self._restore:
+            for t in self._tables:
+                if "ema" not in t:
+                    self._seed_ema(t)
+
+    def _seed_ema(self, t):
+        """Allocate the table's flat ``ema`` buffer next to m / v, seed it from the parameters (or from a loaded / carried-over
+        ``state[p]["ema"]``), and build the table swap_ema() launches over: every trainable parameter, with or without a
+        gradient row at the moment."""
+        ema = torch.empty_like(t["m"])
+        rows, off = [], 0
+        with torch.no_grad():
+            for p in t["params"]:
+                view = self._flat_view(ema, off, p)
+                st = self.state[p]
+                src = st["ema"] if "ema" in st else p
+                view.copy_(src.detach())
+                st["ema"] = view
+                for c0 in range(0, p.numel(), CHUNK):
+                    rows.append((p.data_ptr() + 4 * c0, ema.data_ptr() + 4 * (off + c0), min(CHUNK, p.numel() - c0), 0))
+                off += p.numel()
+        arr = np.zeros(len(rows), dtype=np.dtype([("a", "<u8"), ("b", "<u8"), ("n", "<i4"), ("pad", "<i4")]))
+        for i, r in enumerate(rows):
+            arr[i] = r
+        t["ema"] = ema
+        t["swap"] = torch.from_numpy(arr.view(np.uint8).copy()).to(ema.device)
+        t["n_swap"] = len(rows)
+
+    def ema_parameters(self):
+        """The EMA of every trainable parameter, in parameter order: views into the flat buffers (shape and physical element
+        order of the parameter).  Needs set_ema() and built tables (a step(), or build_tables())."""
+        assert self._ema is not None, "ema_parameters() needs set_ema()"
+        self.build_tables()
+        return [self.state[p]["ema"] for t in self._tables for p in t["params"]]
+
+    def build_tables(self):
+        """Build the chunk tables (and the EMA buffers) now instead of at the first step(), if they are missing or stale."""
+        if self._restore or self._tables is None:
+            assert not self._round_open
+            self._build()
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """Exchange the weights and their EMA in place, one dpft_swap_f32 launch per group: afterwards the parameters hold the
+        former EMA bits and the EMA buffer the former parameter bits; a second call restores both.  Covers every trainable
+        parameter of the group, also one that has no gradient at the moment."""
+        assert self._ema is not None, "swap_ema() needs set_ema()"
+        assert not self._round_open, "FusedAdamW.swap_ema between step_segment() and step()"
+        self.build_tables()
+        for t in self._tables:
+            if any(p.data_ptr() != a for p, (a, _) in zip(t["params"], t["ptrs"])):
+                self._build()                                   # a parameter's storage moved: re-point the tables
+                break
+        for t in self._tables:
+            lib.call("dpft_swap_f32", ptr(t["swap"]), t["n_swap"], stream())
+        note_weights_changed()
 
     def last_grad_norm(self):
         """The global gradient norm of the last clipped step BEFORE clipping (what clip_grad_norm_ returns): a device scalar
@@ -144,6 +236,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 [id(p) for p in old[gi]["params"]] == [id(p) for p in ps]
             if keep:
                 m, v, skipped = old[gi]["m"], old[gi]["v"], old[gi]["skipped"]
+                carried = {k: old[gi][k] for k in ("ema", "swap", "n_swap") if k in old[gi]}
             else:
                 total = sum(p.numel() for p in ps)
                 m = torch.zeros(total, dtype=torch.float32, device=dev)
@@ -171,6 +264,8 @@ class FusedAdamW(torch.optim.Optimizer):
                     else:
                         skip_host[ti] = self._step                      # joins now: its own count starts at 0
                     self.state[p] = {"exp_avg": mv, "exp_avg_sq": vv}
+                    if "ema" in st:                                    # re-homed in the group's new buffer by _seed_ema
+                        self.state[p]["ema"] = st["ema"]
                 rows.append((0, 0, 0, 0, 0, ti))                        # marker row (advances skipped[t] when inactive)
                 if p.grad is not None:
                     assert p.grad.dtype == torch.float32 and (self._layout(p) & self._layout(p.grad)), \
@@ -196,11 +291,30 @@ class FusedAdamW(torch.optim.Optimizer):
             tables.append(dict(params=ps, ptrs=self._ptrs(ps), m=m, v=v, skipped=skipped, chunks=chunks,
                                n_chunks=len(rows), active=active, active_host=None, seg_range=seg_range,
                                seg_tensors=seg_tensors, row_tensor=arr["t"].astype(np.int64)))
+            if keep:
+                tables[-1].update(carried)
+            if self._ema is not None and (not keep or "ema" not in carried or
+                                          [p.data_ptr() for p in ps] != [a for a, _ in old[gi]["ptrs"]]):
+                self._seed_ema(tables[-1])
+            elif self._ema is None:
+                for p in ps:
+                    self.state[p].pop("ema", None)
         self._tables = tables
         self._restore = False
         self._partials = None
         if self._clip is not None:
             self._size_partials()
+
+    @torch.no_grad()
+    def launch_tables(self):
+        """The AdamW launches of step() alone, one per group over the tables as they stand: no pointer check, no refresh of the
+        `active` flags, no norm launches, no gate.  It IS an update (the step count advances, parameters, moments and the EMA
+        move, with whatever the gradient buffers hold).  For measurement (tools/ema_cost.py): needs a step() before it."""
+        assert self._tables is not None and not self._restore and not self._round_open, "launch_tables() needs a step() first"
+        self._step += 1
+        for group, t in zip(self.param_groups, self._tables):
+            self._launch(group, t, 0, t["n_chunks"])
+        note_weights_changed()
 
     def set_gate(self, loss: "torch.Tensor" = None):
         """Device-side `if loss > 0` (trainer.py:131) for the NEXT step(): a scalar tensor that stays on the device; the launch
@@ -221,7 +335,10 @@ class FusedAdamW(torch.optim.Optimizer):
         args = (C.c_void_p(t["chunks"].data_ptr() + first * self.CHUNK_BYTES), count, ptr(t["active"]), ptr(t["skipped"]),
                 float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
                 self._step, ptr(getattr(self, "_gate", None)))
-        if self._clip is not None:
+        if self._ema is not None:
+            lib.call("dpft_adamw_ema_f32", *args, ptr(self._clip_record) if self._clip is not None else None,
+                     ptr(t["m"]), ptr(t["ema"]), self._ema[0], self._ema[1], stream())
+        elif self._clip is not None:
             lib.call("dpft_adamw_clip_f32", *args, ptr(self._clip_record), stream())
         else:
             lib.call("dpft_adamw_f32", *args, stream())

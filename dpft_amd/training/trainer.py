@@ -11,6 +11,7 @@ whole-module checkpoint ``<timestamp>_checkpoint_<epoch>.pt`` that ``dpft_amd.mo
 """
 from __future__ import annotations
 
+import contextlib
 import datetime
 import json
 import os
@@ -23,7 +24,7 @@ import torch.distributed as dist
 
 from dpft_amd.training.distributed import GradBucketReducer, broadcast_module
 from dpft_amd.training.loss import build_loss
-from dpft_amd.training.optimizer import FusedAdamW, build_optimizer
+from dpft_amd.training.optimizer import FusedAdamW, build_optimizer, ema_decay_ok
 
 
 class _ScalarLog:
@@ -67,6 +68,85 @@ def parse_clip_grad_norm(value):
     if nonfinite not in ("propagate", "skip"):
         raise ValueError(f"train.clip_grad_norm: nonfinite must be 'propagate' or 'skip', got {nonfinite!r}")
     return float(value), nonfinite
+
+
+def parse_ema(value):
+    """``train.ema`` -> {"decay", "warmup", "validate", "save"}: a number in [0, 1) (the decay), or ``{"decay": d, "warmup":
+    bool, "validate": bool, "save": bool}`` (warmup off, validate and save on when left out).  Anything else is a ValueError."""
+    out = {"warmup": False, "validate": True, "save": True}
+    if isinstance(value, dict):
+        if "decay" not in value or set(value) - {"decay", "warmup", "validate", "save"}:
+            raise ValueError(f"train.ema: expected {{'decay': d, 'warmup': ..., 'validate': ..., 'save': ...}}, got {value!r}")
+        for k in out:
+            if k in value:
+                if not isinstance(value[k], bool):
+                    raise ValueError(f"train.ema: {k} must be true or false, got {value[k]!r}")
+                out[k] = value[k]
+        value = value["decay"]
+    if not ema_decay_ok(value):
+        raise ValueError(f"train.ema: decay must be a number in [0, 1), got {value!r}")
+    out["decay"] = float(value)
+    return out
+
+
+def ema_decay_f32(decay) -> float:
+    """The decay as the kernel receives it: rounded to fp32 (0.99999999 rounds to 1.0 and is refused)."""
+    return float(torch.tensor(float(decay), dtype=torch.float32))
+
+
+def ema_weight(decay, warmup: bool, own: int) -> float:
+    """The lerp weight of a tensor's ``own``-th update, formed as adamw_kernel forms it: w = fp32(1 - d_eff) with d_eff in
+    double, d_eff = the fp32 decay, or with warm-up min(decay, (1 + own) / (10 + own))."""
+    d = ema_decay_f32(decay)
+    if warmup:
+        d = min(d, (1.0 + own) / (10.0 + own))
+    return float(torch.tensor(1.0 - d, dtype=torch.float64).to(torch.float32))
+
+
+class EagerEMA:
+    """The EMA of the weights for any optimizer but FusedAdamW (and for the CPU): a list of tensors next to the trainable
+    parameters, ``ema.lerp_(p, w)`` by ``torch._foreach_lerp_`` after an optimizer.step() that stepped, for the parameters that
+    had a gradient in it.  The same rule, weight and warm-up formula as the fused launch, on host-side per-tensor counts.
+    The averages and counts live here, not in the optimizer's state (FusedAdamW keeps its own in ``state[p]["ema"]``): a run that
+    resumes saves and restores them with state_dict() / load_state_dict(), otherwise the averages re-seed from the weights."""
+
+    def __init__(self, params, decay: float, warmup: bool = False):
+        self.params = [p for p in params if p.requires_grad]
+        self.decay, self.warmup = decay, warmup
+        self.ema = [p.detach().clone() for p in self.params]
+        self.counts = [0] * len(self.params)
+
+    @torch.no_grad()
+    def update(self):
+        by_weight = {}
+        for i, p in enumerate(self.params):
+            if p.grad is None:
+                continue
+            self.counts[i] += 1
+            by_weight.setdefault(ema_weight(self.decay, self.warmup, self.counts[i]), []).append(i)
+        for w, idx in by_weight.items():
+            torch._foreach_lerp_([self.ema[i] for i in idx], [self.params[i].detach() for i in idx], w)
+
+    def state_dict(self):
+        return {"ema": [e.clone() for e in self.ema], "counts": list(self.counts)}
+
+    @torch.no_grad()
+    def load_state_dict(self, state):
+        if len(state["ema"]) != len(self.ema) or len(state["counts"]) != len(self.counts) or \
+                any(s.shape != e.shape for s, e in zip(state["ema"], self.ema)):
+            raise ValueError("EagerEMA.load_state_dict: the state does not match the trainable parameters")
+        for e, s in zip(self.ema, state["ema"]):
+            e.copy_(s)
+        self.counts = [int(c) for c in state["counts"]]
+
+    @torch.no_grad()
+    def swap(self):
+        for p, e in zip(self.params, self.ema):
+            tmp = p.detach().clone()
+            p.detach().copy_(e)
+            e.copy_(tmp)
+        from dpft_amd.hip.lib import note_weights_changed
+        note_weights_changed()
 
 
 class DataParallelTrainer:
@@ -165,6 +245,17 @@ class DataParallelTrainer:
                 # no bucket can be stepped before the norm over all buckets is known (step_segment() would refuse every call):
                 # early AdamW stays off even with DPFT_EARLY_ADAMW=1
                 self.early_adamw = False
+        # Optional extension (the reference keeps none): train.ema = d | {"decay": d, "warmup": ..., "validate": ..., "save": ...}
+        # keeps an exponential moving average of the weights.  FusedAdamW does it inside its one launch (a third flat buffer, no
+        # extra launch, the device-side gate / clip "skip" / per-tensor counts apply by construction); any other optimizer gets
+        # EagerEMA after optimizer.step().  The EMA is a function of parameters every rank holds identically: no new collective.
+        self.ema = parse_ema(train["ema"]) if "ema" in train else None
+        self._ema_eager = None
+        if self.ema is not None:
+            if isinstance(self.optimizer, FusedAdamW):
+                self.optimizer.set_ema(self.ema["decay"], self.ema["warmup"])
+            else:
+                self._ema_eager = EagerEMA(self.model.parameters(), self.ema["decay"], self.ema["warmup"])
         if self.early_adamw:
             self.optimizer.attach_segments([b["params"] for b in self.reducer.buckets])
             self.reducer.on_bucket_final = self.optimizer.step_segment
@@ -278,6 +369,8 @@ class DataParallelTrainer:
                     self._nonfinite_eager += 1
             if not dropped:
                 self.optimizer.step()
+                if self._ema_eager is not None:
+                    self._ema_eager.update()
             if self.clip is not None and isinstance(self.optimizer, FusedAdamW):
                 self.last_grad_norm = self.optimizer.last_grad_norm()      # a view of the clip record: the next step overwrites it
         elif self.clip is not None:
@@ -296,6 +389,27 @@ class DataParallelTrainer:
         if isinstance(self.optimizer, FusedAdamW):
             return self.optimizer.nonfinite_steps()
         return self._nonfinite_eager
+
+    def ema_parameters(self):
+        """The EMA of every trainable parameter, in parameter order (None with the key absent)."""
+        if self.ema is None:
+            return None
+        return self._ema_eager.ema if self._ema_eager is not None else self.optimizer.ema_parameters()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Run the body with the EMA in place of the live weights: swap in (in place, the parameters keep their storage), yield,
+        swap back in ``finally``.  A no-op with ``train.ema`` absent.  BatchNorm running statistics and other buffers are NOT
+        averaged: they are moving averages already, and the EMA weights are evaluated with the live buffers."""
+        if self.ema is None:
+            yield
+            return
+        swap = self._ema_eager.swap if self._ema_eager is not None else self.optimizer.swap_ema
+        swap()
+        try:
+            yield
+        finally:
+            swap()
 
     def _backward_without_engine(self, loss: torch.Tensor) -> bool:
         """Replayed decoder + fused loss: their two backward steps are launched directly (GraphedFuser.backward_from),
@@ -446,7 +560,14 @@ class DataParallelTrainer:
     @torch.no_grad()
     def validate_one_epoch(self, epoch: int, data_loader: Iterable, writer=None) -> Dict[str, float]:
         """trainer.py:162-213: eval-mode forward (the fused inference decoder), loss and metrics on this rank's shard,
-        averaged over steps and ranks.  Returns ``{'loss': ...}`` like the reference (plus the other means)."""
+        averaged over steps and ranks.  Returns ``{'loss': ...}`` like the reference (plus the other means).  With
+        ``train.ema`` set (and its ``validate`` not false) the epoch runs under ema_weights(): what is validated is what ships."""
+        if self.ema is not None and self.ema["validate"]:
+            with self.ema_weights():
+                return self._validate_one_epoch(epoch, data_loader, writer)
+        return self._validate_one_epoch(epoch, data_loader, writer)
+
+    def _validate_one_epoch(self, epoch: int, data_loader: Iterable, writer=None) -> Dict[str, float]:
         self.model.eval()
         self.loss_fn.eval()
         sums: Dict[str, torch.Tensor] = {}
@@ -484,6 +605,15 @@ class DataParallelTrainer:
             tmp = path + ".tmp"
             torch.save(self.model, tmp)
             os.replace(tmp, path)
+        if self.ema is not None and self.ema["save"]:
+            # train.ema: a second file <stem>_ema<ext> next to the first, the module pickled with the EMA in place of the weights
+            # (buffers as they are).  Every rank swaps (its parameters stay identical to the others'), rank 0 writes.
+            stem, ext = osp.splitext(path)
+            with self.ema_weights():
+                if self.rank == 0:
+                    tmp = stem + "_ema" + ext + ".tmp"
+                    torch.save(self.model, tmp)
+                    os.replace(tmp, stem + "_ema" + ext)
         if self.world > 1:
             dist.barrier()
 

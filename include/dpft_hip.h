@@ -813,6 +813,32 @@ int dpft_adamw_clip_f32(const void* chunks, int32_t n_chunks, const int32_t* act
                         const void* record, dpft_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Exponential moving average (EMA) of the weights inside the AdamW launch, an extension: the reference keeps none.
+ *
+ * dpft_adamw_ema_f32: dpft_adamw_clip_f32 (record != NULL) or dpft_adamw_f32 (record == NULL: unclipped) that also keeps
+ * ema += (p_new - ema) * w for every element it updates -- ema.lerp_(p, 1 - d), the rule of
+ * torch.optim.swa_utils.get_ema_multi_avg_fn -- while the new p is still in registers: one more read-modify-write per
+ * element, no extra launch.  Buffer layout: `ema` is a third flat fp32 buffer per table with exactly the offsets of the
+ * moments; the chunk rows stay 40 bytes, the launch gets the table's moment base `m_base` and `ema_base`, and a row's
+ * slice is ema_base + (row.m - m_base).  It has the alignment of m and is accessed the way m is.
+ * w = (float)(1 - d_eff), d_eff in double: d_eff = ema_decay (in [0, 1), crossing the boundary as a float), or with
+ * ema_warmup == 1 min(ema_decay, (1 + own) / (10 + own)), own = step - skipped[t] the tensor's own AdamW step count (step
+ * with skipped == NULL).  Sitting out: a row that dpft_adamw_f32 / dpft_adamw_clip_f32 would not update -- gate not
+ * positive, record->coef < 0, inactive tensor, marker row -- leaves ema untouched: the average of a tensor advances
+ * exactly when the tensor is updated.  p, m, v and skipped come out bit-equal to the launch without the average.
+ *
+ * dpft_swap_f32: exchanges pairs of disjoint fp32 ranges in place (the live weights and their EMA, for validation and
+ * checkpoints; raw pointers, so a parameter's physical element order does not matter and no scratch copy is needed).
+ * rows: device array of {float* a; float* b; int32 n; int32 pad} (24 bytes each), one workgroup of 256 per row; 16-byte
+ * accesses where both pointers are 16-byte aligned and four elements remain, scalar accesses otherwise.
+ * ---------------------------------------------------------------------------------------- */
+int dpft_adamw_ema_f32(const void* chunks, int32_t n_chunks, const int32_t* active, int32_t* skipped, float lr,
+                       float beta1, float beta2, float eps, float weight_decay, int32_t step, const float* gate,
+                       const void* record, const float* m_base, float* ema_base, float ema_decay, int32_t ema_warmup,
+                       dpft_stream_t stream);
+int dpft_swap_f32(const void* rows, int32_t n_rows, dpft_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline`): while started, every dpft_conv2d_nhwc_* call is bracketed
  * by HIP events on its launch stream.  Not thread-safe; do not use inside a graph capture.
  * ---------------------------------------------------------------------------------------- */
