@@ -563,6 +563,24 @@ static int pick_qw(int B, int Q, int V, int which = 0) {      // which: 0 forwar
     return qw;
 }
 
+// The instantiation and the dynamic LDS bytes of the three launches (0 forward, 1 backward (queries), 2 backward (keys /
+// values)): the one statement of the rule, read by the launch functions and by dpft_selfattn_train_tiles.
+struct SaTiles {
+    int qw[3];
+    size_t lds[3];
+};
+static SaTiles sa_tiles(int B, int Q, int V) {
+    SaTiles t;
+    for (int which = 0; which < 3; ++which) t.qw[which] = pick_qw(B, Q, V, which);
+    const size_t common = 48 * 16 + 48;      // in_proj rows + bias
+    const size_t qf = 4 * t.qw[0], qq = 4 * t.qw[1], kt = 4 * t.qw[2];
+    t.lds[0] = ((size_t)Q * 32 + common + qf * TC + qf * TH * 8 * 4) * sizeof(float);       // K, V | Q' tile | slice partials
+    t.lds[1] = ((size_t)Q * 32 + common + 6 * qq * TC + qq * TH + 2 * qq * TC) * sizeof(float);      // K, V | six tiles | dl | R
+    t.lds[2] = ((size_t)Q * 48 + common + 6 * kt * TC) * sizeof(float);                     // Q', dA, lse, delta | six tiles
+    return t;
+}
+constexpr size_t kSaMaxLds = 160 * 1024;
+
 #define SA_DISPATCH(KERNEL, qw, grid, lds, stream, args)                                                    \
     do {                                                                                                    \
         void (*kfn)(SaArgs) = nullptr;                                                                      \
@@ -577,16 +595,22 @@ static int pick_qw(int B, int Q, int V, int which = 0) {      // which: 0 forwar
         }                                                                                                   \
         if ((lds) > 64 * 1024)                                                                              \
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                      160 * 1024);                                                          \
+                                      (int)kSaMaxLds);                                                      \
         hipLaunchKernelGGL(kfn, grid, dim3(256), lds, (hipStream_t)stream, args);                           \
     } while (0)
+
+static int check_sizes(int V, int B, int Q) {
+    DPFT_REQUIRE(V >= 1 && V <= 4 && B > 0 && Q > 0, "selfattn_train: bad sizes (V=%d, B=%d, Q=%d)", V, B, Q);
+    DPFT_REQUIRE((int64_t)V * B * TH * Q * (((Q + 15) >> 4) * 8) < (1ll << 32), "selfattn_train: problem too large for the mask index");
+    return DPFT_OK;
+}
 
 static int fill_common(SaArgs& a, const dpft_sa_params* params, int V, const float* x, int64_t xbs, const float* pos,
                        float p_drop, const int64_t* seed, int salt, int B, int Q) {
     DPFT_REQUIRE(params && x && pos && seed, "selfattn_train: null argument");
-    DPFT_REQUIRE(V >= 1 && V <= 4 && B > 0 && Q > 0, "selfattn_train: bad sizes (V=%d, B=%d, Q=%d)", V, B, Q);
+    const int rc = check_sizes(V, B, Q);
+    if (rc) return rc;
     DPFT_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "selfattn_train: dropout probability must be in [0,1)");
-    DPFT_REQUIRE((int64_t)V * B * TH * Q * (((Q + 15) >> 4) * 8) < (1ll << 32), "selfattn_train: problem too large for the mask index");
     memset(&a, 0, sizeof(a));
     for (int v = 0; v < V; ++v) {
         a.p[v] = params[v];
@@ -612,9 +636,10 @@ extern "C" int dpft_selfattn_train_fwd_f32(const dpft_sa_params* params, int32_t
     if (rc) return rc;
     DPFT_REQUIRE(y1 && lse && attn && zhat && rstd, "selfattn_train_fwd: null output");
     a.y1 = y1; a.lse = lse; a.attn = attn; a.zhat = zhat; a.rstd = rstd;
-    const int qw = pick_qw(B, Q, V), qt = 4 * qw;
-    const size_t lds = ((size_t)Q * 32 + 48 * 16 + 48 + qt * TC + qt * TH * 8 * 4) * sizeof(float);
-    DPFT_REQUIRE(lds <= 160 * 1024, "selfattn_train_fwd: %d queries do not fit the LDS", Q);
+    const SaTiles t = sa_tiles(B, Q, V);
+    const int qw = t.qw[0], qt = 4 * qw;
+    const size_t lds = t.lds[0];
+    DPFT_REQUIRE(lds <= kSaMaxLds, "selfattn_train_fwd: %d queries do not fit the LDS", Q);
     SA_DISPATCH(sa_train_fwd_kernel, qw, dim3(cdiv(Q, qt), V, B), lds, stream, a);
     return check_launch("selfattn_train_fwd");
 }
@@ -637,19 +662,32 @@ extern "C" int dpft_selfattn_train_bwd_f32(const dpft_sa_params* params, int32_t
     a.dy1 = dy1; a.lse = const_cast<float*>(lse); a.attn = const_cast<float*>(attn); a.zhat = const_cast<float*>(zhat);
     a.rstd = const_cast<float*>(rstd); a.dx = dx; a.dxp = dxp;
     a.dA = scratch; a.delta = scratch + (size_t)V * B * Q * TC;
-    int qw = pick_qw(B, Q, V, 1), qt = 4 * qw;
-    const size_t lds_q = ((size_t)Q * 32 + 48 * 16 + 48 + 6 * qt * TC + qt * TH + std::max(2 * qt * TC, 0)) * sizeof(float);
-    DPFT_REQUIRE(lds_q <= 160 * 1024, "selfattn_train_bwd: %d queries do not fit the LDS", Q);
+    const SaTiles t = sa_tiles(B, Q, V);
+    int qw = t.qw[1], qt = 4 * qw;
+    const size_t lds_q = t.lds[1];
+    DPFT_REQUIRE(lds_q <= kSaMaxLds, "selfattn_train_bwd: %d queries do not fit the LDS", Q);
     SA_DISPATCH(sa_train_bwd_q_kernel, qw, dim3(cdiv(Q, qt), V, B), lds_q, stream, a);
     rc = check_launch("selfattn_train_bwd_q");
     if (rc) return rc;
-    qw = pick_qw(B, Q, V, 2); qt = 4 * qw;
-    const size_t lds_kv = ((size_t)Q * 48 + 48 * 16 + 48 + 6 * qt * TC) * sizeof(float);
-    DPFT_REQUIRE(lds_kv <= 160 * 1024, "selfattn_train_bwd: %d queries do not fit the LDS", Q);
+    qw = t.qw[2]; qt = 4 * qw;
+    const size_t lds_kv = t.lds[2];
+    DPFT_REQUIRE(lds_kv <= kSaMaxLds, "selfattn_train_bwd: %d queries do not fit the LDS", Q);
     SA_DISPATCH(sa_train_bwd_kv_kernel, qw, dim3(cdiv(Q, qt), V, B), lds_kv, stream, a);
     return check_launch("selfattn_train_bwd_kv");
 }
 
 extern "C" int64_t dpft_selfattn_train_scratch_floats(int32_t B, int32_t Q, int32_t V) {
     return (int64_t)V * B * Q * (TC + TH);
+}
+
+extern "C" int dpft_selfattn_train_tiles(int32_t B, int32_t Q, int32_t V, int32_t qw[3], int64_t lds_bytes[3]) {
+    DPFT_REQUIRE(qw && lds_bytes, "selfattn_train_tiles: null output");
+    const int rc = check_sizes(V, B, Q);
+    if (rc) return rc;
+    const SaTiles t = sa_tiles(B, Q, V);
+    for (int i = 0; i < 3; ++i) {
+        qw[i] = t.qw[i];
+        lds_bytes[i] = (int64_t)t.lds[i];
+    }
+    return DPFT_OK;
 }

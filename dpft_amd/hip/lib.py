@@ -153,6 +153,7 @@ SIGNATURES = {
     "dpft_selfattn_train_fwd_f32": (_I, [_P, _I, _P, _L, _P, _F, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P]),
     "dpft_selfattn_train_bwd_f32": (_I, [_P, _I, _P, _L, _P, _F, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "dpft_selfattn_train_scratch_floats": (_L, [_I, _I, _I]),
+    "dpft_selfattn_train_tiles": (_I, [_I, _I, _I, C.POINTER(_I * 3), C.POINTER(_L * 3)]),
     "dpft_xattn_ffn_train_row_floats": (_L, []),
     "dpft_head_train_row_floats": (_L, []),
     "dpft_head_train_fwd_f32": (_I, [C.POINTER(HeadTrain), _I, _I, _I, _P]),

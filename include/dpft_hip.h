@@ -506,6 +506,11 @@ int dpft_selfattn_train_bwd_f32(const dpft_sa_params* params, int32_t V, const f
                                 const float* rstd, const dpft_sa_grads* grads, float* dx, float* dxp,
                                 float* scratch, int32_t B, int32_t Q, dpft_stream_t stream);
 int64_t dpft_selfattn_train_scratch_floats(int32_t B, int32_t Q, int32_t V);
+/* host only, no launch: the compiled tile form (queries / keys per wave: 1, 2, 3, 4, 5, 6 or 8; a block holds four waves)
+ * and the dynamic LDS bytes that the forward, the backward over queries and the backward over keys / values -- in that
+ * order -- use for these sizes, from the code the two launch functions read (the DPFT_SA_QW_FWD / DPFT_SA_QW_BWD /
+ * DPFT_SA_KW tuning variables included).  Same size checks as the launches. */
+int dpft_selfattn_train_tiles(int32_t B, int32_t Q, int32_t V, int32_t qw[3], int64_t lds_bytes[3]);
 
 /* ------------------------------------------------------------------------------------------
  * Training path of the decoder's deformable cross-attention + FFN block, all V views of one MPFusion layer:

@@ -39,17 +39,18 @@ def _keep(idx, which, seed, salt, stream_id, p):
     return np.where(field >= np.uint64(thr), 1.0 / (1.0 - p), 0.0)
 
 
-def self_attn_masks(seed: int, salt: int, p: float, V: int, B: int, Q: int, heads: int = 8, C: int = 16):
+def self_attn_masks(seed: int, salt: int, p: float, V: int, B: int, Q: int, heads: int = 8, C: int = 16, view0: int = 0):
     """-> att (V,B,heads,Q,Q) keep-scales of the attention probabilities (stream 0: one hash per key pair (k, k+8) of a
-    16-key group), d1 (V,B,Q,C) keep-scales of dropout1 (stream 1: one hash per channel pair)."""
+    16-key group), d1 (V,B,Q,C) keep-scales of dropout1 (stream 1: one hash per channel pair).  With ``view0`` the V views
+    are views view0 .. view0 + V - 1 of a larger call (one view at a time keeps a large case small)."""
     KP = ((Q + 15) >> 4) * 8
-    vb = np.arange(V * B, dtype=np.uint64).reshape(V * B, 1, 1, 1)
+    vb = np.arange(view0 * B, (view0 + V) * B, dtype=np.uint64).reshape(V * B, 1, 1, 1)
     h = np.arange(heads, dtype=np.uint64).reshape(1, heads, 1, 1)
     q = np.arange(Q, dtype=np.uint64).reshape(1, 1, Q, 1)
     k = np.arange(Q, dtype=np.uint64).reshape(1, 1, 1, Q)
     idx = (((vb * np.uint64(heads) + h) * np.uint64(Q) + q) * np.uint64(KP) + (k >> np.uint64(4)) * np.uint64(8) + (k & np.uint64(7))) & M32
     att = _keep(idx, np.broadcast_to((k >> np.uint64(3)) & np.uint64(1), idx.shape), seed, salt, 0, p).reshape(V, B, heads, Q, Q)
-    row = np.arange(V * B * Q, dtype=np.uint64).reshape(-1, 1)
+    row = np.arange(view0 * B * Q, (view0 + V) * B * Q, dtype=np.uint64).reshape(-1, 1)
     c = np.arange(C, dtype=np.uint64).reshape(1, C)
     d1 = _keep((row * np.uint64(8) + (c >> np.uint64(1))) & M32, np.broadcast_to(c & np.uint64(1), (V * B * Q, C)), seed, salt, 1, p)
     return att, d1.reshape(V, B, Q, C)
