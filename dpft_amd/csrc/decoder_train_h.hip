@@ -280,6 +280,33 @@ __global__ __launch_bounds__(256) void hd_train_bwd_kernel(HdArgs a) {
     row[HR_H2 + lane] = f.h2;
 }
 
+// Backward of the reference points of a center that is itself differentiable (iteration 0 with a learned querent): what
+// hd_train_bwd_kernel does for the center it has just made, for prev_center -- the same ref_point<true> per view, the same order of
+// the view sum.  One wave per (b, query), lane v = view v.
+__global__ __launch_bounds__(256) void ref_points_bwd_kernel(HdArgs a) {
+    __shared__ float sm[4][12];
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int bq = blockIdx.x * 4 + wv;
+    if (bq >= a.B * a.Q) return;
+    const int b = bq / a.Q;
+    const size_t nq = (size_t)a.B * a.Q;
+    float* dcv = sm[wv];        // [4][3] d center through each view's reference point
+    if (lane < 12) dcv[lane] = 0.f;
+    __builtin_amdgcn_wave_barrier();
+    if (lane < a.V) {
+        const int v = lane;
+        const float* c = a.prev_center + (size_t)bq * 3;
+        const float* dr = a.drefs + ((size_t)v * nq + bq) * 2;
+        float dc[3];
+        ref_point<true>(c[0], c[1], c[2], a.flag[v], a.T[v] ? a.T[v] + (size_t)b * 16 : nullptr,
+                        a.Pm[v] + (size_t)b * a.prow[v] * 4, (float)a.shape[v][b * a.sstride + 0], (float)a.shape[v][b * a.sstride + 1],
+                        dr[0], dr[1], dc);
+        dcv[v * 3 + 0] = dc[0]; dcv[v * 3 + 1] = dc[1]; dcv[v * 3 + 2] = dc[2];
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (lane < 3) a.dcenter_prev[(size_t)bq * 3 + lane] = 0.f + dcv[lane] + dcv[3 + lane] + dcv[6 + lane] + dcv[9 + lane];
+}
+
 }  // namespace dpft
 
 using namespace dpft;
@@ -342,4 +369,17 @@ extern "C" int dpft_head_train_bwd_f32(const dpft_head_train* h, int32_t B, int3
     }
     hipLaunchKernelGGL(hd_train_bwd_kernel, dim3(cdiv((int64_t)B * Q, 4)), dim3(256), 0, (hipStream_t)stream, a);
     return check_launch("head_train_bwd");
+}
+
+extern "C" int dpft_ref_points_bwd_f32(const dpft_head_train* h, int32_t B, int32_t Q, int32_t V, dpft_stream_t stream) {
+    HdArgs a;
+    DPFT_REQUIRE(h && !h->y3, "ref_points_bwd: takes prev_center alone (y3 must be null)");
+    int rc = hd_fill(a, h, B, Q, V, false);
+    if (rc) return rc;
+    DPFT_REQUIRE(h->drefs && h->dcenter_prev, "ref_points_bwd: drefs / dcenter_prev is null");
+    a.drefs = h->drefs; a.dcenter_prev = h->dcenter_prev;
+    rc = hd_check_proj(a, V);
+    if (rc) return rc;
+    hipLaunchKernelGGL(ref_points_bwd_kernel, dim3(cdiv((int64_t)B * Q, 4)), dim3(256), 0, (hipStream_t)stream, a);
+    return check_launch("ref_points_bwd");
 }

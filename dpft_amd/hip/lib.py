@@ -158,6 +158,9 @@ SIGNATURES = {
     "dpft_head_train_row_floats": (_L, []),
     "dpft_head_train_fwd_f32": (_I, [C.POINTER(HeadTrain), _I, _I, _I, _P]),
     "dpft_head_train_bwd_f32": (_I, [C.POINTER(HeadTrain), _I, _I, _I, _P]),
+    "dpft_ref_points_bwd_f32": (_I, [C.POINTER(HeadTrain), _I, _I, _I, _P]),
+    "dpft_query_center_fwd_f32": (_I, [_P, _I, _P, _I, _I, _P]),
+    "dpft_query_center_bwd_f32": (_I, [_P, _P, _I, _P, _I, _I, _P]),
     "dpft_xattn_ffn_train_saved_floats": (_L, []),
     "dpft_xattn_ffn_train_scratch_floats": (_L, []),
     "dpft_xattn_ffn_train_fwd_f32": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _F, _P, _I, _P, _P, _I, _I, _P]),

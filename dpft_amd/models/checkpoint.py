@@ -182,10 +182,14 @@ def infer_config(model: nn.Module) -> Dict[str, Any]:
             transformation = _TRANSFORMATIONS[tname]
         else:
             raise ValueError(f"checkpoint: querent transformation {tname!r} cannot be mapped")
-        cfg_model["querent"] = {"name": "data_agnostic_static_querent", "transformation": transformation,
-                                "resolution": list(_attr(querent, "resolution")),
-                                "minimum": list(_attr(querent, "minimum")), "maximum": list(_attr(querent, "maximum")),
-                                "distribution": list(_hyper(querent, "distribution", "linear", "querent"))}
+        grid = {"transformation": transformation, "resolution": list(_attr(querent, "resolution")),
+                "minimum": list(_attr(querent, "minimum")), "maximum": list(_attr(querent, "maximum"))}
+        if "queries" in querent._parameters:      # LearnableQueries (src/dprt/models/queries/learnable.py): owns its points
+            cfg_model["querent"] = {"name": "learnable_querent", **grid,
+                                    "q_init": _hyper(querent, "q_init", "uniform_", "querent")}
+        else:
+            cfg_model["querent"] = {"name": "data_agnostic_static_querent", **grid,
+                                    "distribution": list(_hyper(querent, "distribution", "linear", "querent"))}
     if fuser is not None and _attr(fuser, "i_iter") is not None:
         keys = ("i_iter", "m_views", "d_model", "d_ffn", "n_queries", "n_levels", "n_heads", "n_points", "norm", "dropout",
                 "reduction", "activation", "ffn_layer")

@@ -56,7 +56,7 @@ class _Replay(torch.autograd.Function):
         ops.memops([(s, a) for s, a in zip(g.static_inputs, inputs[:len(g.static_inputs)]) if s.data_ptr() != a.data_ptr()])
         g.fwd_graph.replay()
         ctx.g = g
-        g.last_inputs = inputs[1:1 + g.n_levels]            # this step's pyramid tensors (see backward_from)
+        g.last_inputs = inputs[g.first_diff:1 + g.n_levels]      # this step's differentiable inputs (see backward_from)
         if not g.clone_outputs:                             # the caller consumes the outputs before the next replay
             return tuple(o.detach() for o in g.static_outputs)
         return tuple(o.detach().clone() for o in g.static_outputs)
@@ -71,10 +71,12 @@ class _Replay(torch.autograd.Function):
         # The static gradient buffers are handed out as they are: their consumers (embedding / FPN backward,
         # gradient accumulation) run before the next replay overwrites them.
         gi = [None if t is None else t.detach() for t in g.static_grad_inputs]
+        n_in = 1 + g.n_levels - g.first_diff                     # (a learned querent's centres +) the pyramid tensors
+        gin = [None] * g.first_diff + gi[:n_in]
         if g.grad_direct is not None:      # the graph already added the parameter gradients into the buckets
             g.grad_direct.mark_ready_many(g.params_with_grad)
-            return (None, None, *gi[:g.n_levels], *([None] * (n_other + len(g.params))))
-        return (None, None, *gi[:g.n_levels], *([None] * n_other), *gi[g.n_levels:])
+            return (None, *gin, *([None] * (n_other + len(g.params))))
+        return (None, *gin, *([None] * n_other), *gi[n_in:])
 
 
 class GraphedFuser:
@@ -101,8 +103,9 @@ class GraphedFuser:
     def backward_from(self, write_output_grads) -> None:
         """The backward of the replayed decoder WITHOUT the autograd engine in front of it: ``write_output_grads`` fills
         ``static_grad_outputs`` (center, size, angle, class) in place, the backward graph is launched at once, and only
-        then autograd is started on the pyramid tensors with the graph's input gradients -- the engine's start-up
-        (~0.2 ms on the host, after the step's host sync, with an idle GPU) hides behind the decoder's backward."""
+        then autograd is started on the pyramid tensors (and a learned querent's centres) with the graph's input gradients --
+        the engine's start-up (~0.2 ms on the host, after the step's host sync, with an idle GPU) hides behind the decoder's
+        backward."""
         levels = self.last_inputs
         self.last_inputs = None
         write_output_grads(self.static_grad_outputs)
@@ -110,10 +113,10 @@ class GraphedFuser:
         if self.grad_direct is not None:
             self.grad_direct.mark_ready_many(self.params_with_grad)
         else:
-            for p, t in zip(self.params, self.static_grad_inputs[self.n_levels:]):
+            for p, t in zip(self.params, self.static_grad_inputs[len(levels):]):
                 if t is not None:
                     p.grad = t.detach().clone() if p.grad is None else p.grad.add_(t)
-        pairs = [(l, t.detach()) for l, t in zip(levels, self.static_grad_inputs[:self.n_levels])
+        pairs = [(l, t.detach()) for l, t in zip(levels, self.static_grad_inputs[:len(levels)])
                  if t is not None and l.requires_grad]
         torch.autograd.backward([l for l, _ in pairs], [t for _, t in pairs])
 
@@ -130,8 +133,15 @@ class GraphedFuser:
         proj = model._get_projetions(self.inputs, sample_batch)
         self.flags = model.fuser.transformation_flags(proj)
         self.level_keys = [list(feats[i].keys()) for i in self.inputs]
-        center0 = model.querent(sample_batch)["center"]
-        static = [center0.detach()]          # the querent's cached constant: the same storage every step, never copied
+        with torch.enable_grad():            # (whether the centres are learned must not depend on the caller's grad mode)
+            center0 = model.querent(sample_batch)["center"]
+        if center0.requires_grad:
+            # a learned querent: its centres are an input like the pyramids -- a buffer of the graph's own that every step's
+            # centres are copied into (_Replay.forward), differentiable, its gradient handed on to the querent's backward
+            static = [center0.detach().clone().requires_grad_(True)]
+        else:
+            static = [center0.detach()]      # the querent's cached constant: the same storage every step, never copied
+        self.first_diff = 0 if center0.requires_grad else 1      # index of the first differentiable static input
         for i in self.inputs:
             static += [v.detach().clone().requires_grad_(True) for v in feats[i].values()]
         self.n_levels = len(static) - 1
@@ -145,7 +155,7 @@ class GraphedFuser:
         self.params = [p for p in self.flat.parameters() if p.requires_grad]
         self.static_inputs = static
         self.shapes = [tuple(s.shape) for s in static]
-        diff_inputs = static[1:1 + self.n_levels] + self.params
+        diff_inputs = static[self.first_diff:1 + self.n_levels] + self.params
 
         # warm-up on a side stream (lazy initialisations, allocator growth) -- nothing is accumulated into .grad
         side = torch.cuda.Stream()
@@ -166,13 +176,14 @@ class GraphedFuser:
         # the launch is captured against an empty DEVICE table that is filled right after
         add_table = torch.empty((max(len(self.params), 1), 3), dtype=torch.int64, device=center0.device) if grad_direct is not None else None
         add_rows = []
+        n_in = 1 + self.n_levels - self.first_diff
         with torch.enable_grad(), torch.cuda.graph(self.bwd_graph, capture_error_mode=CAPTURE_MODE):   # its own private pool (see module docstring)
             grads = torch.autograd.grad(self.static_outputs, diff_inputs, self.static_grad_outputs,
                                         allow_unused=True)
             from dpft_amd.models.fusers import train_fused as _tf
             _tf.join_forked()      # the weight-gradient branches of the capture end here
             if grad_direct is not None:
-                pairs = [(grad_direct.grad_buffer(p), t) for p, t in zip(self.params, grads[self.n_levels:]) if t is not None]
+                pairs = [(grad_direct.grad_buffer(p), t) for p, t in zip(self.params, grads[n_in:]) if t is not None]
                 if any(v is None for v, _ in pairs):
                     raise RuntimeError("GraphedFuser: a decoder parameter is not owned by the gradient reducer")
                 plain = [(v, t) for v, t in pairs if v.is_contiguous() and t.is_contiguous() and v.numel() == t.numel()
@@ -187,7 +198,7 @@ class GraphedFuser:
             add_table[:len(add_rows)].copy_(torch.tensor(add_rows, dtype=torch.int64))
         self._add_table = add_table
         self.static_grad_inputs = list(grads)
-        self.params_with_grad = [p for p, t in zip(self.params, grads[self.n_levels:]) if t is not None]
+        self.params_with_grad = [p for p, t in zip(self.params, grads[n_in:]) if t is not None]
         torch.cuda.synchronize()
         # inference replay: eval mode (dropout off, MHA fast path), no autograd
         self.flat.eval()

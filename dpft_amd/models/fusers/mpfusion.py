@@ -247,7 +247,11 @@ class IMPFusion(nn.Module):
                 # (one summation launch in the backward instead of a reduction per block + autograd's add chain); the
                 # learned query table goes in as it is -- the first layer broadcasts it over the batch itself
                 pos_hub = _tf.make_pos_hub(self.query_embedding.weight)
-                refs = _tf.reference_points(proj, out["center"])
+                c0 = out["center"]
+                if c0.requires_grad:      # a learned querent: the iteration-0 reference points pass their gradient on to it
+                    refs = _tf.RefPointsFn.apply(proj, c0 if c0.shape[-1] == 3 else c0[..., :3])
+                else:
+                    refs = _tf.reference_points(proj, c0)
                 query = self.query
                 for it, (layer, head) in enumerate(zip(layers, self.heads)):
                     y3 = layer.forward_fused_blocks(query, pyramids, refs, pos_hub, seed, it, batch=B)

@@ -401,6 +401,30 @@ def reference_points(proj: _Proj, center: torch.Tensor) -> torch.Tensor:
     return refs
 
 
+class RefPointsFn(torch.autograd.Function):
+    """``reference_points`` of a center that carries a gradient (a learned querent's output): the same forward launch, and
+    dpft_ref_points_bwd_f32 -- the rule the head blocks apply to the centers they make -- back to the center."""
+
+    @staticmethod
+    def forward(ctx, proj: _Proj, center):
+        center = center.contiguous().float()
+        ctx.save_for_backward(center)
+        ctx.proj = proj
+        return reference_points(proj, center)
+
+    @staticmethod
+    def backward(ctx, drefs):
+        (center,) = ctx.saved_tensors
+        B, Q, _ = center.shape
+        drefs = drefs.contiguous()
+        dcenter = torch.empty_like(center)
+        h = HeadTrain()
+        ctx.proj.fill(h)
+        h.prev_center, h.drefs, h.dcenter_prev, h.num_classes = center.data_ptr(), drefs.data_ptr(), dcenter.data_ptr(), 1
+        lib.call("dpft_ref_points_bwd_f32", C.byref(h), B, Q, len(ctx.proj.T), stream())
+        return None, dcenter
+
+
 def _fill_head_weights(h: HeadTrain, weights, packed):
     h.packed, h.red_w = packed.data_ptr(), weights[0].data_ptr()
     for g in range(4):

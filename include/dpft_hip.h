@@ -577,6 +577,34 @@ int dpft_head_train_fwd_f32(const dpft_head_train* h, int32_t B, int32_t Q, int3
 int dpft_head_train_bwd_f32(const dpft_head_train* h, int32_t B, int32_t Q, int32_t V, dpft_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Backward of the reference points of a center that was NOT made by a head: the querent's output when it is learned
+ * (LearnableQueries, src/dprt/models/queries/learnable.py; the forward is dpft_head_train_fwd_f32 with y3 == NULL).
+ *   dcenter_prev[b][q] = sum_v  d refs[v][b][q] / d prev_center[b][q] ^T  drefs[v][b][q]
+ * Reads of `h`: prev_center (B,Q,3), drefs (V,B,Q,2), T / P / p_rows / shape / shape_stride / has_t; writes dcenter_prev
+ * (B,Q,3).  y3 must be NULL.  The rule is the one dpft_head_train_bwd_f32 applies to the center it makes, conventions
+ * included: a coordinate outside the clip [0,1] passes no gradient; w == 0 passes the gradient of the undivided
+ * coordinates; r == 0 and rho^2 == 0 pass none through the norm / elevation and the azimuth; the arcsin slope is
+ * clamped at 1e15.  Views are summed in index order.
+ * ---------------------------------------------------------------------------------------- */
+int dpft_ref_points_bwd_f32(const dpft_head_train* h, int32_t B, int32_t Q, int32_t V, dpft_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Learned query points (LearnableQueries.forward, src/dprt/models/queries/learnable.py:103-128): the (Q,3) parameter
+ * repeated over the batch and transformed, center[b][q] = f(queries[q]), with f by `mode`: the identity, or Spher2Cart
+ * (src/dprt/models/utils/transformations.py:212-281) of (r, phi, roh) in radians or degrees:
+ *   (r cos(phi) cos(roh), r sin(phi) cos(roh), r sin(roh))
+ * Backward: dqueries[q] = J_f(queries[q])^T sum_b dcenter[b][q]; the batch is summed by one thread, b ascending, so the
+ * result is the same bits on every call (no atomics).  queries, dqueries (Q,3); center, dcenter (B,Q,3); B*Q*3 < 2^31.
+ * ---------------------------------------------------------------------------------------- */
+#define DPFT_QUERY_IDENTITY 0
+#define DPFT_QUERY_SPHER2CART_RAD 1
+#define DPFT_QUERY_SPHER2CART_DEG 2
+int dpft_query_center_fwd_f32(const float* queries, int32_t mode, float* center, int32_t B, int32_t Q,
+                              dpft_stream_t stream);
+int dpft_query_center_bwd_f32(const float* dcenter, const float* queries, int32_t mode, float* dqueries, int32_t B,
+                              int32_t Q, dpft_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Weight gradients of the fused training decoder from the per-row factor matrices its backward kernels write:
  *   out[g][out_off + a * n_b + b] = sum_r rows[g][r][col_a + a] * rows[g][r][col_b + b]     (a < n_a, b < n_b)
  * col_b < 0 (with n_b == 1): column sums of the a-columns.  rows (G,R,W); specs is a HOST array of <= 40 entries;
