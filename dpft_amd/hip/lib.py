@@ -138,6 +138,8 @@ SIGNATURES = {
     "dpft_fpn_output_f32": (_I, [_DESC, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dpft_msda_fwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "dpft_msda_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "dpft_msda_fwd_typed": (_I, [_P] * 6 + [_I] * 9 + [_P]),
+    "dpft_msda_bwd_typed": (_I, [_P] * 10 + [_I] * 9 + [_P]),
     "dpft_xattn_fwd_f32": (_I, [_PYR, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dpft_xattn_bwd_f32": (_I, [_PYR, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dpft_giou3d_yaw_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),

@@ -518,7 +518,60 @@ def add_pos_(x, pos_x, pos_y):
     return x
 
 
+MSDA_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}      # the `dtype` argument of dpft_msda_*_typed
+
+
+def _msda_operands(value, loc, attn, grad_out=None):
+    """The operator's dtype rule: ``value`` is float32, float16 or bfloat16 on the GPU and sets the storage type; ``loc`` is
+    float32 or value's type; ``attn`` / ``grad_out`` of another float type are cast to value's (upstream's ``type_as``).
+    Anything else raises here: the kernels read raw pointers and would take the bytes for what they are not."""
+    if value.dtype not in MSDA_DTYPES:
+        raise HipLibraryError(f"msda: value must be float32, float16 or bfloat16, not {value.dtype}")
+    for name, t in (("value", value), ("loc", loc), ("attn", attn), ("grad_out", grad_out)):
+        if t is not None and not t.is_cuda:
+            raise TypeError(f"msda: {name} is on {t.device}; dpft_amd ops need CUDA (ROCm) tensors, there is no CPU path")
+    if loc.dtype not in (torch.float32, value.dtype):
+        raise HipLibraryError(f"msda: loc must be float32 or value's {value.dtype}, not {loc.dtype}")
+    for name, t in (("attn", attn), ("grad_out", grad_out)):
+        if t is not None and not t.is_floating_point():
+            raise HipLibraryError(f"msda: {name} must be a floating-point tensor, not {t.dtype}")
+    attn = attn.to(value.dtype).contiguous()
+    if grad_out is not None:
+        grad_out = grad_out.to(value.dtype).contiguous()
+    return value.contiguous(), loc.contiguous(), attn, grad_out
+
+
+def msda_fwd_typed(value, shapes, lsi, loc, attn):
+    """dpft_msda_fwd_typed for every storage type, float32 (dtype = 0) included; out has value's type."""
+    value, loc, attn, _ = _msda_operands(value, loc, attn)
+    N, S, M, D = value.shape
+    _, Lq, _, L, P, _ = loc.shape
+    out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
+    lib.call("dpft_msda_fwd_typed", ptr(value), ptr(shapes), ptr(lsi), ptr(loc), ptr(attn), ptr(out), N, S, M, D, Lq, L, P,
+             MSDA_DTYPES[value.dtype], int(loc.dtype == torch.float32), stream())
+    return out
+
+
+def msda_bwd_typed(value, shapes, lsi, loc, attn, grad_out):
+    """dpft_msda_bwd_typed -> (grad_value, grad_loc, grad_attn) in the types of value, loc, value.  The fp32 sums of a 16-bit
+    grad_value live in a scratch tensor of N*S*M*D floats; the entry clears what it adds into."""
+    value, loc, attn, grad_out = _msda_operands(value, loc, attn, grad_out)
+    N, S, M, D = value.shape
+    _, Lq, _, L, P, _ = loc.shape
+    gv = torch.empty_like(value)
+    gl = torch.empty_like(loc)
+    ga = torch.empty_like(attn)
+    ws = None if value.dtype == torch.float32 else torch.empty(value.numel(), dtype=torch.float32, device=value.device)
+    lib.call("dpft_msda_bwd_typed", ptr(value), ptr(shapes), ptr(lsi), ptr(loc), ptr(attn), ptr(grad_out), ptr(gv), ptr(gl),
+             ptr(ga), ptr(ws), N, S, M, D, Lq, L, P, MSDA_DTYPES[value.dtype], int(loc.dtype == torch.float32), stream())
+    return gv, gl, ga
+
+
 def msda_fwd(value, shapes, lsi, loc, attn):
+    """The operator by value's dtype: float32 -> dpft_msda_fwd_f32, float16 / bfloat16 -> dpft_msda_fwd_typed."""
+    if value.dtype != torch.float32:
+        return msda_fwd_typed(value, shapes, lsi, loc, attn)
+    value, loc, attn, _ = _msda_operands(value, loc, attn)
     N, S, M, D = value.shape
     _, Lq, _, L, P, _ = loc.shape
     out = torch.empty((N, Lq, M * D), dtype=torch.float32, device=value.device)
@@ -528,6 +581,9 @@ def msda_fwd(value, shapes, lsi, loc, attn):
 
 
 def msda_bwd(value, shapes, lsi, loc, attn, grad_out):
+    if value.dtype != torch.float32:
+        return msda_bwd_typed(value, shapes, lsi, loc, attn, grad_out)
+    value, loc, attn, grad_out = _msda_operands(value, loc, attn, grad_out)
     N, S, M, D = value.shape
     _, Lq, _, L, P, _ = loc.shape
     gv = torch.zeros_like(value)

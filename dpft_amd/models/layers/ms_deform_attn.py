@@ -23,13 +23,21 @@ from dpft_amd.hip import ops
 
 
 class MSDeformAttnFunction(Function):
-    """Operator-level drop-in for the MSDA extension (ms_deform_attn.py:27-68) on the C-ABI."""
+    """Operator-level drop-in for the MSDA extension (ms_deform_attn.py:27-68) on the C-ABI.  ``value`` float32, float16 or
+    bfloat16 sets the storage type of the kernels (ops.msda_fwd); under autocast the locations and the softmax weights arrive
+    as float32 beside a 16-bit value: the locations go to the kernels as they are, the weights are cast to value's type, and
+    every gradient comes back in the dtype its input arrived in."""
 
     @staticmethod
     def forward(ctx, value, value_spatial_shapes, value_level_start_index, sampling_locations,
                 attention_weights, im2col_step):
         ctx.im2col_step = im2col_step
+        ctx.in_dtypes = (sampling_locations.dtype, attention_weights.dtype)
         value, sampling_locations = value.contiguous(), sampling_locations.contiguous()
+        if sampling_locations.dtype != value.dtype and sampling_locations.is_floating_point():
+            sampling_locations = sampling_locations.float()
+        if attention_weights.is_floating_point():
+            attention_weights = attention_weights.to(value.dtype)
         attention_weights = attention_weights.contiguous()
         shapes = value_spatial_shapes.to(torch.int64).contiguous()
         lsi = value_level_start_index.to(torch.int64).contiguous()
@@ -42,7 +50,7 @@ class MSDeformAttnFunction(Function):
     def backward(ctx, grad_output):
         value, shapes, lsi, loc, attn = ctx.saved_tensors
         gv, gl, ga = ops.msda_bwd(value, shapes, lsi, loc, attn, grad_output.contiguous())
-        return gv, None, None, gl, ga, None
+        return gv, None, None, gl.to(ctx.in_dtypes[0]), ga.to(ctx.in_dtypes[1]), None
 
 
 class PyramidState:

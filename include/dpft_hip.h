@@ -15,6 +15,9 @@
  *   dpft_msda_fwd_f32 / dpft_msda_bwd_f32
  *       MSDA.ms_deform_attn_forward / ms_deform_attn_backward, the only native seam the
  *       reference has: src/dprt/models/layers/ms_deform_attn.py:24,32-39,58-66.
+ *   dpft_msda_fwd_typed / dpft_msda_bwd_typed
+ *       the same seam with fp32, half or bf16 storage (upstream's extension takes half too: the door mixed-precision
+ *       training comes through).
  *   dpft_xattn_fwd_f32 / dpft_xattn_bwd_f32
  *       the flatten+cat -> value_proj -> MSDA core chain of MLFusion.forward_cross_attn /
  *       MSDeformAttn.forward: src/dprt/models/fusers/mpfusion.py:150-208 and
@@ -376,6 +379,20 @@ int dpft_msda_bwd_f32(const float* value, const int64_t* shapes, const int64_t* 
                       const float* loc, const float* attn, const float* grad_out,
                       float* grad_value, float* grad_loc, float* grad_attn, int32_t N, int32_t S,
                       int32_t M, int32_t D, int32_t Lq, int32_t L, int32_t P, dpft_stream_t stream);
+/* The same operator with typed storage (msda_typed.hip).  dtype: 0 fp32 | 1 IEEE half | 2 bf16 -- the type of value, attn,
+ * out, grad_out, grad_value and grad_attn.  loc32 = 1: loc and grad_loc are fp32 whatever dtype is (what autocast hands
+ * over); loc32 = 0: they have type dtype.  All arithmetic is fp32; every result is rounded to its type once, to nearest even.
+ * Any M, D >= 1; the forward uses 16-byte accesses when D % 8 == 0 (D % 4 for fp32) and value / out are 16-byte aligned.
+ * Backward: grad_value is summed by fp32 atomics in `workspace` (N*S*M*D floats; required for dtype != 0, ignored for 0,
+ * where grad_value itself takes the sums) and rounded to dtype by a last pass.  The entry clears the sums itself on
+ * `stream`: unlike dpft_msda_bwd_f32, nothing has to be zero-filled by the caller.  No allocation, no synchronisation. */
+int dpft_msda_fwd_typed(const void* value, const int64_t* shapes, const int64_t* lsi, const void* loc,
+                        const void* attn, void* out, int32_t N, int32_t S, int32_t M, int32_t D, int32_t Lq,
+                        int32_t L, int32_t P, int32_t dtype, int32_t loc32, dpft_stream_t stream);
+int dpft_msda_bwd_typed(const void* value, const int64_t* shapes, const int64_t* lsi, const void* loc,
+                        const void* attn, const void* grad_out, void* grad_value, void* grad_loc, void* grad_attn,
+                        float* workspace, int32_t N, int32_t S, int32_t M, int32_t D, int32_t Lq, int32_t L,
+                        int32_t P, int32_t dtype, int32_t loc32, dpft_stream_t stream);
 
 #define DPFT_MAX_LEVELS 8
 typedef struct dpft_pyramid {
