@@ -16,6 +16,7 @@
 //           bound |q| max|k| in the exp2 domain (1/sqrt(d) log2(e) folded into q; exact two-pass redo should a
 //           query underflow), two queries per packed-fp32 operation, slice partials merged through LDS.  Writes the
 //           pre-out_proj attention output.  Iteration 0 runs for ONE batch element (its input does not depend on b).
+//           Q + 50 > 512: decoder_scores_head_long_kernel, the same launch with the rows staged in trips of 512 items.
 //       head blocks   (wave = (b, q)) of the PREVIOUS iteration: 48->16 view reduction, the 4 head MLPs,
 //           center += previous, and the next reference points of all views.  Both kinds depend only on the previous
 //           cross-attention kernel, so the head MLPs' latency chain hides behind the scores.
@@ -308,7 +309,8 @@ struct ScoreArgs {
 
 // COMPOSED = false: first layer -- the rows are constants of the weights (learned query table + embedding), read as packed
 // COMPOSED = true : rows = packed position part + sum over the source views of the partials the previous xattn wrote
-template <bool COMPOSED>
+// MULTI = false: Q + QC <= 512, one staging trip (straight-line code); MULTI = true: as many trips of 512 items as Q needs
+template <bool COMPOSED, bool MULTI>
 __device__ __forceinline__ void scores_block(const ScoreArgs& a, float* sm, int sid) {
     const int Q = a.Q, SL = (Q + NS - 1) / NS;
     f32x4* KV = reinterpret_cast<f32x4*>(sm);                     // [Q + NS] (k0,k1,v0,v1); one pad entry per slice
@@ -329,41 +331,45 @@ __device__ __forceinline__ void scores_block(const ScoreArgs& a, float* sm, int 
         // whole row: its input is the learned query table) [+ COMPOSED: the V partial projections the previous
         // cross-attention kernel wrote].  Those lines were written by other XCDs a moment ago (first touch = a fabric
         // round trip of ~2 us): all loads of the thread's items are issued before the first one is consumed.
+        // Two items per thread and trip: one trip covers Q + QC <= 512 items (every Q up to 512 - QC, the product's 400
+        // included; decoder_scores_head_kernel); larger Q take further trips of 512 items (decoder_scores_head_long_kernel).
         constexpr int NIT = 2;
-        static_assert(QC <= 112, "two items per thread cover Q + QC <= 512");
-        f32x4 t4[NIT], p4[NIT][4];
+        static_assert(QC <= 112, "the one-trip form covers Q + QC <= 512 up to the product's Q = 400");
+        for (int base = 0; base < (MULTI ? Q + QC : 1); base += NIT * 256) {
+            f32x4 t4[NIT], p4[NIT][4];
 #pragma unroll
-        for (int u = 0; u < NIT; ++u) {
-            const int i = tid + u * 256;
-            const bool isq = i >= Q;
-            const int k = isq ? min(q0 + i - Q, Q - 1) : i;
-            if (i < Q + QC) t4[u] = *reinterpret_cast<const f32x4*>(pi + PC_T + ((size_t)h * Q + k) * 8 + (isq ? 0 : 4));
-            if (COMPOSED && i < Q + QC) {
-                // partials: kv (V targets,B,8 heads,V sources,Q,4) then q (same shape, q0 q1 - -): a block's reads
-                // (one target, batch element and head; lanes = consecutive keys) are contiguous; one load type for both
-                // item kinds (a select between a dwordx2 and a dwordx4 load serialises them)
-                const size_t grp = (((size_t)view * a.B + b) * 8 + h) * a.V;
-                const float* src = a.part + (isq ? (size_t)a.V * a.B * 8 * a.V * Q * 4 : 0) + (grp * Q + k) * 4;
+            for (int u = 0; u < NIT; ++u) {
+                const int i = base + tid + u * 256;
+                const bool isq = i >= Q;
+                const int k = isq ? min(q0 + i - Q, Q - 1) : i;
+                if (i < Q + QC) t4[u] = *reinterpret_cast<const f32x4*>(pi + PC_T + ((size_t)h * Q + k) * 8 + (isq ? 0 : 4));
+                if (COMPOSED && i < Q + QC) {
+                    // partials: kv (V targets,B,8 heads,V sources,Q,4) then q (same shape, q0 q1 - -): a block's reads
+                    // (one target, batch element and head; lanes = consecutive keys) are contiguous; one load type for both
+                    // item kinds (a select between a dwordx2 and a dwordx4 load serialises them)
+                    const size_t grp = (((size_t)view * a.B + b) * 8 + h) * a.V;
+                    const float* src = a.part + (isq ? (size_t)a.V * a.B * 8 * a.V * Q * 4 : 0) + (grp * Q + k) * 4;
 #pragma unroll
-                for (int v = 0; v < 4; ++v)
-                    if (v < a.V) p4[u][v] = *reinterpret_cast<const f32x4*>(src + (size_t)v * Q * 4);
+                    for (int v = 0; v < 4; ++v)
+                        if (v < a.V) p4[u][v] = *reinterpret_cast<const f32x4*>(src + (size_t)v * Q * 4);
+                }
             }
-        }
 #pragma unroll
-        for (int u = 0; u < NIT; ++u) {
-            const int i = tid + u * 256;
-            if (i >= Q + QC) break;
-            const bool isq = i >= Q;
-            f32x4 r = t4[u];                                       // q items: lanes 2,3 unused
-            if (COMPOSED) {
+            for (int u = 0; u < NIT; ++u) {
+                const int i = base + tid + u * 256;
+                if (i >= Q + QC) break;
+                const bool isq = i >= Q;
+                f32x4 r = t4[u];                                       // q items: lanes 2,3 unused
+                if (COMPOSED) {
 #pragma unroll
-                for (int v = 0; v < 4; ++v)
-                    if (v < a.V) r += p4[u][v];
-            }
-            if (isq) Qs[i - Q] = f32x2{r[0], r[1]};
-            else {
-                KV[i + i / SL] = r;
-                atomicMax(kmax + i / SL, __float_as_uint(fmaf(r[0], r[0], r[1] * r[1])));      // >= 0: uint order = float order
+                    for (int v = 0; v < 4; ++v)
+                        if (v < a.V) r += p4[u][v];
+                }
+                if (isq) Qs[i - Q] = f32x2{r[0], r[1]};
+                else {
+                    KV[i + i / SL] = r;
+                    atomicMax(kmax + i / SL, __float_as_uint(fmaf(r[0], r[0], r[1] * r[1])));      // >= 0: uint order = float order
+                }
             }
         }
     }
@@ -932,8 +938,23 @@ __global__ __launch_bounds__(256, DEC_SH_BLOCKS) void decoder_scores_head_kernel
     const int n_head_blocks = (int)gridDim.x - n_score;
     const int bid = (int)blockIdx.x < n_head_blocks ? n_score + (int)blockIdx.x : (int)blockIdx.x - n_head_blocks;
     if (bid < n_score) {
-        if (composed == 1) scores_block<true>(sa, sm, bid);
-        else scores_block<false>(sa, sm, bid);
+        if (composed == 1) scores_block<true, false>(sa, sm, bid);
+        else scores_block<false, false>(sa, sm, bid);
+    } else {
+        reduce_head_block(ha, hs, bid - n_score);
+    }
+}
+
+// The same launch for Q + QC > 512: the score blocks stage their rows in several trips.  A kernel of its own, so that the
+// one above stays the straight-line code the product's Q = 400 runs.
+__global__ __launch_bounds__(256, DEC_SH_BLOCKS) void decoder_scores_head_long_kernel(ScoreArgs sa, HeadArgs ha, int n_score, int composed) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    __shared__ float hs[4][2][64];
+    const int n_head_blocks = (int)gridDim.x - n_score;
+    const int bid = (int)blockIdx.x < n_head_blocks ? n_score + (int)blockIdx.x : (int)blockIdx.x - n_head_blocks;
+    if (bid < n_score) {
+        if (composed == 1) scores_block<true, true>(sa, sm, bid);
+        else scores_block<false, true>(sa, sm, bid);
     } else {
         reduce_head_block(ha, hs, bid - n_score);
     }
@@ -1018,6 +1039,21 @@ extern "C" int dpft_decoder_pack_infer_f32(const dpft_decoder_view* view, int32_
 
 constexpr int XR = 7;      // query rows (waves) per decoder_xattn_kernel block: 3 blocks of 51 KB LDS per CU
 
+// dynamic LDS of a score block: K/V rows (one pad entry per slice) | slice maxima | query rows | slice partials
+constexpr int SCORE_ONE_TRIP = 512;      // items (keys + a chunk's queries) of decoder_scores_head_kernel's one staging trip
+constexpr size_t SCORE_LDS_MAX = 62 * 1024;
+constexpr size_t score_lds_bytes(int64_t Q) { return (4 * (size_t)(Q + NS) + SC_W + 2 * QC + 4 * QC * NS) * sizeof(float); }
+constexpr int SCORE_MAX_Q = (int)((SCORE_LDS_MAX / sizeof(float) - SC_W - 2 * QC - 4 * QC * NS) / 4 - NS);
+static_assert(score_lds_bytes(SCORE_MAX_Q) <= SCORE_LDS_MAX && score_lds_bytes(SCORE_MAX_Q + 1) > SCORE_LDS_MAX, "largest admitted Q");
+
+// The limits the launches below use (HOST code, no launch): queries per score block, key slices per score block, query rows
+// per cross-attention block, largest n_queries the score kernel's LDS admits.
+extern "C" int dpft_decoder_limits(int32_t out[4]) {
+    DPFT_REQUIRE(out, "decoder_limits: null output");
+    out[0] = QC; out[1] = NS; out[2] = XR; out[3] = SCORE_MAX_Q;
+    return DPFT_OK;
+}
+
 // Whole IMPFusion forward from ONE call: 2 launches per iteration + 1, nothing else on the host:
 //   [scores(0)] [xattn(0)] [scores(1) | heads(0)] [xattn(1)] ... [scores(I-1) | heads(I-2)] [xattn(I-1)] [heads(I-1)]
 extern "C" int dpft_decoder_forward_f32(const dpft_decoder_fwd* d, dpft_stream_t stream) {
@@ -1027,6 +1063,7 @@ extern "C" int dpft_decoder_forward_f32(const dpft_decoder_fwd* d, dpft_stream_t
     const int B = d->B, Q = d->Q, V = d->V;
     DPFT_REQUIRE(B > 0 && Q > 0 && V >= 1 && V <= 4 && d->iters >= 1 && d->iters <= 8, "decoder_forward: bad sizes");
     DPFT_REQUIRE(d->num_classes >= 1 && d->num_classes <= 16, "decoder_forward: num_classes must be in [1,16]");
+    DPFT_REQUIRE(Q <= SCORE_MAX_Q, "decoder_forward: %d queries do not fit the LDS of the score kernel (at most %d)", Q, SCORE_MAX_Q);
     const size_t nq = (size_t)B * Q;
     float* w = d->work;
     float* qbuf[2] = {w, w + nq * DC};
@@ -1070,10 +1107,10 @@ extern "C" int dpft_decoder_forward_f32(const dpft_decoder_fwd* d, dpft_stream_t
     ha.size = d->size; ha.angle = d->angle; ha.cls = d->cls;
     sa.part = part; sa.pos = d->pos; sa.attn = attn; sa.B = B; sa.Q = Q; sa.V = V;
     sa.nchunk = cdiv(Q, QC);
-    const size_t lds1 = (4 * (size_t)(Q + NS) + SC_W + 2 * QC + 4 * QC * NS) * sizeof(float);
+    const size_t lds1 = score_lds_bytes(Q);
     const size_t lds2 = ((size_t)K2_FLOATS + XR * XW_FLOATS) * sizeof(float);
-    DPFT_REQUIRE(lds1 <= 62 * 1024, "decoder_forward: %d queries do not fit the LDS of the score kernel", Q);
     const int n_head = cdiv((int64_t)nq, 4);
+    const auto score_kernel = Q + QC > SCORE_ONE_TRIP ? decoder_scores_head_long_kernel : decoder_scores_head_kernel;
     const float* query = d->query0;
     const float* center = d->center0;
     for (int it = 0; it <= d->iters; ++it) {
@@ -1099,7 +1136,7 @@ extern "C" int dpft_decoder_forward_f32(const dpft_decoder_fwd* d, dpft_stream_t
         // weights; with d->attn0 (dpft_decoder_attn0_f32, made when the weights are packed) the launch disappears
         const bool skip = first && d->attn0 != nullptr;
         if (!skip) {
-            hipLaunchKernelGGL(decoder_scores_head_kernel, dim3(n_score + (first ? 0 : n_head)), dim3(256),
+            hipLaunchKernelGGL(score_kernel, dim3(n_score + (first ? 0 : n_head)), dim3(256),
                                after_last ? 0 : lds1, (hipStream_t)stream, sa, ha, n_score, first ? 0 : 1);
             RC(check_launch("decoder_scores_head"));
         }
@@ -1146,10 +1183,11 @@ extern "C" int dpft_decoder_attn0_f32(const float* packed_views, const float* po
     for (int v = 0; v < V; ++v) sa.pi[v] = packed_views + (size_t)v * pi_floats(Q);      // iteration 0's blobs
     sa.pos = pos; sa.attn = attn0; sa.B = 1; sa.Bsa = 1; sa.Q = Q; sa.V = V;
     sa.nchunk = cdiv(Q, QC);
-    const size_t lds1 = (4 * (size_t)(Q + NS) + SC_W + 2 * QC + 4 * QC * NS) * sizeof(float);
-    DPFT_REQUIRE(lds1 <= 62 * 1024, "decoder_attn0: %d queries do not fit the LDS of the score kernel", Q);
+    const size_t lds1 = score_lds_bytes(Q);
+    DPFT_REQUIRE(Q <= SCORE_MAX_Q, "decoder_attn0: %d queries do not fit the LDS of the score kernel (at most %d)", Q, SCORE_MAX_Q);
     const int n_score = sa.nchunk * DM * V;
-    hipLaunchKernelGGL(decoder_scores_head_kernel, dim3(n_score), dim3(256), lds1, (hipStream_t)stream, sa, ha, n_score, 0);
+    hipLaunchKernelGGL(Q + QC > SCORE_ONE_TRIP ? decoder_scores_head_long_kernel : decoder_scores_head_kernel, dim3(n_score),
+                       dim3(256), lds1, (hipStream_t)stream, sa, ha, n_score, 0);
     return check_launch("decoder_attn0");
 }
 

@@ -10,12 +10,22 @@ from typing import Dict, List, Optional, Tuple
 import torch
 from torch import nn
 
-from dpft_amd.hip.lib import DecoderFwd, DecoderView, Pyramid, lib, make_pyramid, stream, weights_generation
+from dpft_amd.hip.lib import DecoderFwd, DecoderView, HipLibraryError, Pyramid, lib, make_pyramid, stream, weights_generation
+
+
+def limits() -> Tuple[int, int, int, int]:
+    """(queries per score block, key slices per score block, query rows per cross-attention block, largest n_queries) of the
+    kernels, from the library (host code)."""
+    out = (C.c_int32 * 4)()
+    lib.call("dpft_decoder_limits", out)
+    return tuple(out)
 
 
 def supported(fuser: nn.Module) -> bool:
     from dpft_amd.models.heads.detection import LinearDetectionHead
     try:
+        if not 1 <= fuser.n_queries <= limits()[3]:      # the score kernel keeps all keys of a head in LDS
+            return False
         ok = (fuser.d_model == 16 and fuser.d_ffn == 32 and fuser.norm and fuser.reduction == "linear"
               and fuser.activation == "Mish" and 1 <= fuser.m_views <= 4
               and all(h == 8 for h in fuser.n_heads)
@@ -43,6 +53,10 @@ def _view_struct(ml: nn.Module) -> Tuple[DecoderView, list]:
 
 class FusedDecoder:
     def __init__(self, fuser: nn.Module):
+        max_q = limits()[3]
+        if fuser.n_queries > max_q:      # refused here, before anything is packed or launched
+            raise HipLibraryError(f"fused decoder: {fuser.n_queries} queries do not fit the LDS of the score kernel "
+                                  f"(at most {max_q})")
         self.fuser = fuser
         self._key = None
 

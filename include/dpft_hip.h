@@ -492,6 +492,10 @@ typedef struct dpft_decoder_fwd {
 int dpft_decoder_attn0_f32(const float* packed_views, const float* pos, int32_t Q, int32_t V, float* attn0,
                            dpft_stream_t stream);
 int64_t dpft_decoder_work_floats(int32_t B, int32_t Q, int32_t V);
+/* HOST code, no launch: the limits the decoder launches use -- out[0] queries per score block, out[1] key slices per score
+ * block, out[2] query rows per cross-attention block, out[3] the largest Q that dpft_decoder_forward_f32 and
+ * dpft_decoder_attn0_f32 admit (LDS of the score kernel); a larger Q is refused by both */
+int dpft_decoder_limits(int32_t out[4]);
 /* measurement aid: with DPFT_DEC_DBG=1024 in the environment the decoder kernels stamp a 100 MHz clock at their phase
  * boundaries; copies 2 kernels x 2048 blocks x 8 slots of uint64 (last launches) to dst (tools/decoder_stamps.py) */
 int dpft_debug_decoder_stamps(uint64_t* dst);
