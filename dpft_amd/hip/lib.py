@@ -176,6 +176,8 @@ SIGNATURES = {
     "dpft_set_loss_scratch_floats": (_L, [_I, _I]),
     "dpft_set_loss_fwd_total_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(_F * 5), _F, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "dpft_set_loss_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(_F * 5), _F, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "dpft_giou_loss_fwd_f32": (_I, [_P] * 6 + [_F] + [_P] * 4 + [_I] * 3 + [_P]),
+    "dpft_giou_loss_bwd_f32": (_I, [_P] * 6 + [_F] + [_P] * 4 + [_I] * 4 + [_P]),
     "dpft_resize_bilinear_nhwc_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dpft_resize_bilinear_nhwc_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dpft_scale_clip_f32": (_I, [_P, _P, _L, _F, _F, _F, _F, _P]),

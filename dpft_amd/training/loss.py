@@ -10,9 +10,13 @@ Differences in execution only: GIoU3D comes from the HIP kernel ``dpft_giou3d_ya
 yaw-only box geometry instead of pytorch3d.box3d_overlap, src/dprt/utils/iou.py:121-210), and the
 B per-sample ``C.cpu()`` syncs (assigner.py:135) are one padded device->host copy per step;
 ``scipy.optimize.linear_sum_assignment`` still runs on the host (indices must be bit-exact).
+One addition the reference cannot offer (its GIoULoss, loss.py:111-173, needs pytorch3d and has no backward): the optional
+``loss_weights["giou"]`` term, a differentiable GIoU3D over the matched pairs (``_GiouLossFn``, csrc/giou_loss.hip); off by
+default, and with the key absent nothing here runs differently.
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Any, Dict, List, Tuple
 
@@ -253,6 +257,46 @@ class _SetLossFn(torch.autograd.Function):
         return dcls, dcenter, dsize, dangle, None, None, None, None, None, None, None, None
 
 
+class _GiouLossFn(torch.autograd.Function):
+    """dpft_giou_loss_fwd/bwd_f32 (csrc/giou_loss.hip): the optional GIoU3D term of the matched pairs and the total with it,
+    (center, size, angle, total_in) -> (term, total_out = total_in + term).  Both scalars come out of the forward launch: adding
+    the term costs no ATen launch, and the gradient of ``total_out`` passes through to ``total_in`` unchanged."""
+
+    @staticmethod
+    def forward(ctx, center, size, angle, total_in, gt_box, match, counts, w_giou, grad_targets=None):
+        from dpft_amd.hip.lib import lib, stream
+        B, N = center.shape[:2]
+        Mmax = gt_box.shape[1]
+        term = torch.empty((), dtype=torch.float32, device=center.device)
+        total = torch.empty((), dtype=torch.float32, device=center.device)
+        lib.call("dpft_giou_loss_fwd_f32", center.data_ptr(), size.data_ptr(), angle.data_ptr(), gt_box.data_ptr(),
+                 match.data_ptr(), counts.data_ptr(), w_giou, total_in.data_ptr(), term.data_ptr(), total.data_ptr(), None,
+                 B, N, Mmax, stream())
+        if grad_targets is not None:
+            # the five-term gradient is already on its way into these buffers (dpft_assign_loss*_f32 launched it): this
+            # term's share is added right behind it on the same stream, d total / d term = 1
+            dcenter, dsize, dangle = grad_targets
+            lib.call("dpft_giou_loss_bwd_f32", center.data_ptr(), size.data_ptr(), angle.data_ptr(), gt_box.data_ptr(),
+                     match.data_ptr(), counts.data_ptr(), w_giou, None, dcenter.data_ptr(), dsize.data_ptr(),
+                     dangle.data_ptr(), 1, B, N, Mmax, stream())
+        ctx.save_for_backward(center, size, angle, gt_box, match, counts)
+        ctx.w_giou = w_giou
+        ctx.mark_non_differentiable(term)
+        return term, total
+
+    @staticmethod
+    def backward(ctx, _gterm, gtotal):
+        from dpft_amd.hip.lib import lib, stream
+        center, size, angle, gt_box, match, counts = ctx.saved_tensors
+        B, N = center.shape[:2]
+        gout = gtotal.contiguous().float()
+        dcenter, dsize, dangle = (torch.empty_like(t) for t in (center, size, angle))
+        lib.call("dpft_giou_loss_bwd_f32", center.data_ptr(), size.data_ptr(), angle.data_ptr(), gt_box.data_ptr(),
+                 match.data_ptr(), counts.data_ptr(), ctx.w_giou, gout.data_ptr(), dcenter.data_ptr(), dsize.data_ptr(),
+                 dangle.data_ptr(), 0, B, N, gt_box.shape[1], stream())
+        return dcenter, dsize, dangle, gtotal, None, None, None, None, None
+
+
 class Loss(nn.modules.loss._Loss):
     def __init__(self, anassigner: nn.Module = None, criterion: nn.Module = None, loss_weights: Dict[str, float] = None,
                  reduction: str = "mean", **kwargs):
@@ -264,6 +308,10 @@ class Loss(nn.modules.loss._Loss):
         self.anassigner, self.criterion = anassigner, criterion
         self.loss_weights = loss_weights if loss_weights is not None else {}
         self.reduction = reduction
+        if self._GIOU in self.loss_weights:
+            w = self.loss_weights[self._GIOU]
+            if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(w) or w < 0:
+                raise ValueError(f"loss_weights['{self._GIOU}'] must be a finite number >= 0, got {w!r}")
 
     @classmethod
     def from_config(cls, config: Dict[str, Any]) -> "Loss":
@@ -274,11 +322,15 @@ class Loss(nn.modules.loss._Loss):
 
     use_fused = True      # CUDA: matcher cost, criterion and its gradient from 3 HIP kernels (dpft_amd/csrc/misc.hip)
     _TERMS = ("total_class", "object_class", "center", "size", "angle")
+    # Optional sixth term, off by default (the reference cannot offer one: its GIoULoss needs pytorch3d and has no backward):
+    # the differentiable GIoU3D of the matched pairs, w / B * sum_b mean_k (1 - G) / 2 -- csrc/giou_loss.hip, DESIGN.md 3.  It
+    # has its own two launches behind the five-term ones and exists on the fused path only.
+    _GIOU = "giou"
 
     def _fused_ok(self, inputs) -> bool:
         return (self.use_fused and inputs["class"].is_cuda and self.reduction == "mean"
                 and isinstance(self.anassigner, HungarianAnassigner) and isinstance(self.criterion, SetCriterion)
-                and set(self.loss_weights) <= set(self._TERMS) and inputs["class"].dtype == torch.float32)
+                and set(self.loss_weights) <= set(self._TERMS) | {self._GIOU} and inputs["class"].dtype == torch.float32)
 
     # Assignments on the device (csrc/lsap.hip) instead of a read-back + host assignment.  Off by default for a stand-alone Loss:
     # scipy raises ValueError for a cost matrix with NaN / inf entries AT the call, a kernel can only leave a status word; the
@@ -417,8 +469,9 @@ class Loss(nn.modules.loss._Loss):
                 self.__dict__["_bwd_written"] = tuple(tg)
             losses5, total = _SetLossFn.apply(cls, center, size, angle, gt_box, gt_onehot, match_t, counts_m, weights5, 0.75, sel,
                                               (losses5, total))
+            total, giou = self._giou_term(center, size, angle, total, gt_box, match_t, counts_m, tg if ok_t else None)
             self.__dict__["_last"] = (cls, center, size, angle, gt_box, gt_onehot, match_t, counts_m, weights5, 0.75, sel, total)
-            return total, {k: losses5[self._TERMS.index(k)] for k in self.loss_weights}
+            return total, self._batch_losses(losses5, giou)
         host = self._to_host(cost)                                         # the host path's sync (assign_on_device has none)
         if use_c:
             # The whole host window in ONE C call (dpft_assign_loss_f32, csrc/cabi.cpp): the batch's assignments (scipy's algorithm
@@ -438,6 +491,7 @@ class Loss(nn.modules.loss._Loss):
                 self.__dict__["_bwd_written"] = tuple(tg)
             losses5, total = _SetLossFn.apply(cls, center, size, angle, gt_box, gt_onehot, match_t, counts_m, weights5, 0.75, sel,
                                               (losses5, total))
+            total, giou = self._giou_term(center, size, angle, total, gt_box, match_t, counts_m, tg if ok_t else None)
         else:      # A/B switch: scipy per sample, separate launches
             packed[:] = -1
             match = packed[:B * Mmax * 2].reshape(B, Mmax, 2)
@@ -449,9 +503,32 @@ class Loss(nn.modules.loss._Loss):
             packed[B * Mmax * 2:] = counts
             packed_t.copy_(pin[:n_pack], non_blocking=True)
             losses5, total = _SetLossFn.apply(cls, center, size, angle, gt_box, gt_onehot, match_t, counts_m, weights5, 0.75, sel)
+            total, giou = self._giou_term(center, size, angle, total, gt_box, match_t, counts_m, None)
         self.__dict__["_last"] = (cls, center, size, angle, gt_box, gt_onehot, match_t, counts_m, weights5, 0.75, sel, total)
-        batch_losses = {k: losses5[self._TERMS.index(k)] for k in self.loss_weights}        # views, for logging
-        return total, batch_losses
+        return total, self._batch_losses(losses5, giou)
+
+    def _giou_term(self, center, size, angle, total, gt_box, match, counts, grad_targets):
+        """(total, None) with the key absent -- no launch, the five-term total as it is.  Otherwise (total + term, term) from the
+        GIoU forward launch, which reads the match table and the matched counts where the assignment left them on the device;
+        ``grad_targets`` = the (dcenter, dsize, dangle, dcls) buffers the five-term gradient was launched into during this
+        forward (fused_grad_targets), or None: with grad mode on, the GIoU backward (accumulate form) is launched into them
+        right behind the forward."""
+        self.__dict__["_last_giou"] = None
+        if self._GIOU not in self.loss_weights:
+            return total, None
+        w = float(self.loss_weights[self._GIOU])
+        if grad_targets is not None and not torch.is_grad_enabled():
+            # no_grad: the forward entry only, nothing is added to the caller's buffers.  They hold the five-term gradient alone
+            # then, so they do not count as written: a backward_into() into them launches both gradients
+            grad_targets = self.__dict__["_bwd_written"] = None
+        term, total = _GiouLossFn.apply(center, size, angle, total, gt_box, match, counts, w,
+                                        None if grad_targets is None else tuple(grad_targets[:3]))
+        self.__dict__["_last_giou"] = w
+        return total, term
+
+    def _batch_losses(self, losses5, giou):
+        """The configured terms in the order of ``loss_weights`` (views, for logging)."""
+        return {k: giou if k == self._GIOU else losses5[self._TERMS.index(k)] for k in self.loss_weights}
 
     def backward_into(self, total: torch.Tensor, dcenter, dsize, dangle, dcls) -> bool:
         """d total / d (center, size, angle, class) of the LAST fused forward, written into the given buffers by the one
@@ -459,6 +536,7 @@ class Loss(nn.modules.loss._Loss):
         import ctypes as C
         from dpft_amd.hip.lib import lib, stream
         last = self.__dict__.pop("_last", None)
+        w_giou = self.__dict__.pop("_last_giou", None)
         if last is None or last[-1] is not total:
             return False
         cls, center, size, angle, gt_box, gt_onehot, match, counts, weights5, alpha, sel, _ = last
@@ -473,13 +551,21 @@ class Loss(nn.modules.loss._Loss):
                  gt_box.data_ptr(), gt_onehot.data_ptr(), match.data_ptr(), counts.data_ptr(), C.byref(w), alpha,
                  sel.data_ptr(), dcls.data_ptr(), dcenter.data_ptr(), dsize.data_ptr(), dangle.data_ptr(), B, N,
                  gt_box.shape[1], ncls, stream())
+        if w_giou is not None:      # the GIoU term's share, added to the rows the launch above has just written
+            lib.call("dpft_giou_loss_bwd_f32", center.data_ptr(), size.data_ptr(), angle.data_ptr(), gt_box.data_ptr(),
+                     match.data_ptr(), counts.data_ptr(), w_giou, None, dcenter.data_ptr(), dsize.data_ptr(),
+                     dangle.data_ptr(), 1, B, N, gt_box.shape[1], stream())
         return True
 
     def forward(self, inputs: Dict[str, torch.Tensor], targets: List[Dict[str, torch.Tensor]]):
         self.__dict__.pop("_last", None)
+        self.__dict__.pop("_last_giou", None)
         self.__dict__["last_has_targets"] = None      # (None = unknown: the eager path)
         if self._fused_ok(inputs):
             return self.forward_fused(inputs, targets)
+        if self._GIOU in self.loss_weights:
+            raise ValueError("loss_weights['giou']: the GIoU term exists on the fused path only (CUDA tensors, fp32 outputs, "
+                             "reduction 'mean', use_fused); there is no eager or CPU implementation of it")
         return self.forward_eager(inputs, targets)
 
     def forward_eager(self, inputs: Dict[str, torch.Tensor], targets: List[Dict[str, torch.Tensor]]):

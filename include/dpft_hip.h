@@ -770,6 +770,28 @@ int dpft_set_loss_bwd_f32(const float* cls, const float* center, const float* si
                           int32_t Mmax, int32_t C, dpft_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Optional sixth criterion term (train.loss_weights["giou"]; the reference's GIoULoss, src/dprt/training/loss.py:111-173, needs
+ * pytorch3d and has no backward): the differentiable GIoU3D of the matched pairs,
+ *   term = w_giou / B * sum_b 1 / counts[b] * sum_k (1 - G(pred[b, i_k], gt[b, j_k])) / 2,      (i_k, j_k) = match[b, k]
+ * match (B,Mmax,2) and counts (B) as the assignment entries leave them.  G = the matcher's yaw-box GIoU3D in fp64 with
+ * union = v1 + v2 - vol always (the textbook value for disjoint boxes, not the reference's constant -1) and
+ * yaw = atan2(sin, cos) in fp64, differentiated through; an invalid box (min(lw, lh, wh) / 2 <= 1e-4 or a size <= 0) gives
+ * G = -1 and no gradient.  One workgroup, fp64 sums in a fixed order: repeated launches give the same bits.
+ * fwd: term (1 float) and, when total_in / total_out (device scalars, both or neither) are given, total_out = total_in + term;
+ *      g_pairs (B,Mmax), may be NULL: G per pair slot (0 in empty slots).
+ * bwd: d (gout * term) / d (center, size, angle); gout = DEVICE scalar, NULL = 1.  accumulate = 0: all B * N rows are written
+ *      (zeros for unmatched queries); accumulate = 1: the fp32-rounded gradient is added to the matched rows only (bit-equal
+ *      to the write form followed by an fp32 add).
+ * ---------------------------------------------------------------------------------------- */
+int dpft_giou_loss_fwd_f32(const float* center, const float* size, const float* angle, const float* gt_box,
+                           const int32_t* match, const int32_t* counts, float w_giou, const float* total_in, float* term,
+                           float* total_out, float* g_pairs, int32_t B, int32_t N, int32_t Mmax, dpft_stream_t stream);
+int dpft_giou_loss_bwd_f32(const float* center, const float* size, const float* angle, const float* gt_box,
+                           const int32_t* match, const int32_t* counts, float w_giou, const float* gout, float* dcenter,
+                           float* dsize, float* dangle, int32_t accumulate, int32_t B, int32_t N, int32_t Mmax,
+                           dpft_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Input preprocessing on the device (the reference does it per sample in DataLoader workers):
  * camera frame resize = torchvision.transforms.functional.resize(bilinear, no antialias) on the HWC frame
  * (src/dprt/datasets/kradar/dataset.py:319-341), from fp32 or straight from the decoded u8 bytes; radar map scaling
