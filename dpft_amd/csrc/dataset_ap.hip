@@ -1,0 +1,376 @@
+// Split-level AP_BEV / AP_3D accumulated on the device during evaluation (dpft_amd/evaluation/dataset_ap.py holds the
+// definition; tests/dataset_ap_ref.py restates it in numpy fp64).
+//
+// update, per batch, two launches, no host read-back:
+//   pair pass   one thread per (sample, query, target): BEV and 3D IoU in fp64 into a (B,N,Mmax,2) scratch.  fp64 end to end (this
+//               file is built with -ffp-contract=off): the strict "IoU > threshold" rule then decides exactly as the fp64 restatement
+//               does, also where an IoU equals a threshold exactly.
+//   match pass  one workgroup per sample: detections compacted and sorted in LDS by (score desc, query asc), then one wave per
+//               (IoU kind, threshold) combination walks them in order; the lanes hold the targets (<= 4 per lane, the "assigned"
+//               bits are lane-private registers), a wave reduction picks the best unassigned target above the threshold.  The
+//               workgroup reserves its records with ONE integer atomic on a device cursor and appends 16-byte records.
+// finalize, once per epoch: one workgroup per (class, combination) scans that class's ordered records (block prefix sum of the TP
+//               bits) into R recall bins (64-bit integer max of the precision's bit pattern), suffix maximum, AP.
+// The clip is this file's own (no relocatable device code in this build); it takes (sin, cos) directly -- no atan2.
+#include "common.h"
+
+#include <limits.h>
+
+namespace dpft {
+
+constexpr int kApMaxN = 1024, kApMaxM = 256, kApMaxC = 16, kApMaxK = 8, kApMaxR = 101;
+// counters (int64): [0] record cursor, [1] queries dropped for a NaN score, [2] records refused for lack of capacity,
+// [16 + c] ground-truth count of class c
+constexpr int kApCursor = 0, kApNan = 1, kApOverflow = 2, kApNpos = 16;
+
+struct ApArgs {
+    const float *cls, *center, *size, *angle;      // (B,N,C) (B,N,3) (B,N,3) (B,N,2)
+    const float* gt_box;                           // (B,Mmax,8)
+    const int32_t* gt_id;                          // (B,Mmax)
+    const int32_t* counts;                         // (B)
+    double* pair;                                  // (B,N,Mmax,2): bev, 3d
+    int4* records;                                 // (capacity): score bits, frame, query | class << 16, TP bits
+    unsigned long long* counters;
+    double thr[kApMaxK];
+    int kind[kApMaxK];                             // 0 bev, 1 3d
+    float roi[6];
+    int has_roi;
+    float min_score;
+    long long capacity;
+    int first_frame;
+    int B, N, Mmax, C, K;
+};
+
+struct ApP2 { double x, y; };
+
+// first maximal entry; a NaN counts as the maximum (torch.max / numpy.argmax)
+__device__ __forceinline__ int ap_argmax(const float* x, int n, float& best) {
+    best = x[0];
+    int arg = 0;
+    for (int k = 1; k < n; ++k) {
+        const float v = x[k];
+        if (v > best || (v != v && best == best)) { best = v; arg = k; }
+    }
+    return arg;
+}
+
+__device__ __forceinline__ bool ap_in_roi(const ApArgs& a, const float* c) {
+    if (!a.has_roi) return true;
+    return (a.roi[0] < c[0]) && (c[0] < a.roi[1]) && (a.roi[2] < c[1]) && (c[1] < a.roi[3]) && (a.roi[4] < c[2]) && (c[2] < a.roi[5]);
+}
+
+__device__ double ap_poly_area(const ApP2* p, int n) {
+    double a = 0;
+    for (int i = 0; i < n; ++i) {
+        const ApP2 u = p[i], v = p[(i + 1) % n];
+        a += u.x * v.y - v.x * u.y;
+    }
+    return a / 2;
+}
+
+// corners (counter-clockwise) of a (center, size, (sin, cos)) box; false = invalid box
+__device__ bool ap_corners(const float* ce, const float* sz, const float* an, ApP2* c) {
+    const double l = sz[0], w = sz[1], h = sz[2], s = an[0], co = an[1];
+    const double r = hypot(s, co);
+    if (!(r > 0)) return false;
+    if (!(fmin(fmin(l * w, l * h), w * h) / 2 > 1e-4)) return false;
+    const double si = s / r, cs = co / r;
+    const double sx[4] = {-1, 1, 1, -1}, sy[4] = {-1, -1, 1, 1};
+    for (int i = 0; i < 4; ++i) {
+        const double x = sx[i] * l / 2, y = sy[i] * w / 2;
+        c[i].x = cs * x - si * y + (double)ce[0];
+        c[i].y = si * x + cs * y + (double)ce[1];
+    }
+    if (ap_poly_area(c, 4) < 0) { const ApP2 t = c[1]; c[1] = c[3]; c[3] = t; }
+    return true;
+}
+
+__device__ void ap_iou_pair(const float* ce1, const float* sz1, const float* an1, const float* ce2, const float* sz2,
+                            const float* an2, double& bev, double& vol3d) {
+    bev = 0;
+    vol3d = 0;
+    ApP2 poly[10], tmp[10], Q[4];
+    if (!ap_corners(ce1, sz1, an1, poly) || !ap_corners(ce2, sz2, an2, Q)) return;
+    int n = 4;
+    for (int e = 0; e < 4 && n > 0; ++e) {      // Sutherland-Hodgman: box 1 clipped by the half-planes of box 2
+        const ApP2 a = Q[e], bb = Q[(e + 1) & 3];
+        int m = 0;
+        for (int k = 0; k < n; ++k) {
+            const ApP2 c = poly[k], d = poly[(k + 1) % n];
+            const double sc = (bb.x - a.x) * (c.y - a.y) - (bb.y - a.y) * (c.x - a.x);
+            const double sd = (bb.x - a.x) * (d.y - a.y) - (bb.y - a.y) * (d.x - a.x);
+            if (sc >= 0) tmp[m++] = c;
+            if ((sc >= 0) != (sd >= 0)) {
+                const double t = sc / (sc - sd);
+                tmp[m].x = c.x + t * (d.x - c.x);
+                tmp[m].y = c.y + t * (d.y - c.y);
+                ++m;
+            }
+        }
+        n = m;
+        for (int k = 0; k < n; ++k) poly[k] = tmp[k];
+    }
+    const double inter = n >= 3 ? fabs(ap_poly_area(poly, n)) : 0.0;
+    const double l1 = sz1[0], w1 = sz1[1], h1 = sz1[2], l2 = sz2[0], w2 = sz2[1], h2 = sz2[2];
+    const double a1 = l1 * w1, a2 = l2 * w2;
+    if (inter > 0) bev = inter / (a1 + a2 - inter);
+    const double z1 = ce1[2], z2 = ce2[2];
+    const double zov = fmax(0.0, fmin(z1 + h1 / 2, z2 + h2 / 2) - fmax(z1 - h1 / 2, z2 - h2 / 2));
+    const double vol = inter * zov;
+    if (vol > 0) vol3d = vol / (a1 * h1 + a2 * h2 - vol);
+}
+
+__global__ __launch_bounds__(128) void ap_pair_kernel(ApArgs a) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (int64_t)a.B * a.N * a.Mmax) return;
+    const int j = (int)(idx % a.Mmax);
+    const int64_t bn = idx / a.Mmax;
+    const int b = (int)(bn / a.N);
+    double bev = 0, d3 = 0;
+    if (j < a.counts[b]) {
+        const int gc = a.gt_id[(int64_t)b * a.Mmax + j];
+        const float* g = a.gt_box + ((int64_t)b * a.Mmax + j) * 8;
+        float best;
+        if (gc != 0 && ap_argmax(a.cls + bn * a.C, a.C, best) == gc && ap_in_roi(a, g) && ap_in_roi(a, a.center + bn * 3))
+            ap_iou_pair(a.center + bn * 3, a.size + bn * 3, a.angle + bn * 2, g, g + 3, g + 6, bev, d3);
+    }
+    a.pair[idx * 2 + 0] = bev;
+    a.pair[idx * 2 + 1] = d3;
+}
+
+__global__ __launch_bounds__(256) void ap_match_kernel(ApArgs a) {
+    __shared__ unsigned long long key[kApMaxN];      // (score descending, query ascending) as one ascending integer
+    __shared__ float score[kApMaxN];
+    __shared__ unsigned tp[kApMaxN];                 // per sorted detection: bit k = TP of combination k
+    __shared__ unsigned char label[kApMaxN];
+    __shared__ unsigned char cand[kApMaxN];          // per sorted detection: bit k = some target lies above threshold k
+    __shared__ int npos[kApMaxC];
+    __shared__ int s_D, s_nan;
+    __shared__ long long s_base;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int N = a.N, C = a.C, M = min(a.counts[b], a.Mmax);
+    if (tid < kApMaxC) npos[tid] = 0;
+    if (tid == 0) { s_D = 0; s_nan = 0; }
+    __syncthreads();
+    // ---- detections of the frame (compacted in arrival order: the sort below fixes the order) and ground-truth counts ----
+    for (int n = tid; n < N; n += 256) {
+        float s;
+        const int l = ap_argmax(a.cls + ((int64_t)b * N + n) * C, C, s);
+        label[n] = (unsigned char)l;
+        score[n] = s;
+        if (l == 0) continue;
+        if (s != s) { atomicAdd(&s_nan, 1); continue; }
+        if (!(s >= a.min_score) || !ap_in_roi(a, a.center + ((int64_t)b * N + n) * 3)) continue;
+        unsigned u = __float_as_uint(s);
+        if (u == 0x80000000u) u = 0u;                                   // -0 orders as +0
+        const unsigned ord = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+        key[atomicAdd(&s_D, 1)] = ((unsigned long long)(~ord) << 32) | (unsigned)n;
+    }
+    for (int j = tid; j < M; j += 256) {
+        const int c = a.gt_id[(int64_t)b * a.Mmax + j];
+        if (c > 0 && c < C && ap_in_roi(a, a.gt_box + ((int64_t)b * a.Mmax + j) * 8)) atomicAdd(&npos[c], 1);
+    }
+    __syncthreads();
+    const int D = s_D;
+    int P = 1;
+    while (P < D) P <<= 1;
+    for (int i = D + tid; i < P; i += 256) key[i] = ~0ull;
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1) {                                  // bitonic sort, ascending
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < P; i += 256) {
+                const int x = i ^ j;
+                if (x > i) {
+                    const unsigned long long u = key[i], v = key[x];
+                    if ((u > v) == ((i & k) == 0)) { key[i] = v; key[x] = u; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    // ---- which detections have a candidate at all (the walk below only stops at those) ----
+    const double* pair = a.pair + (int64_t)b * N * a.Mmax * 2;
+    for (int i = tid; i < D; i += 256) {
+        const double* row = pair + (int64_t)(unsigned)key[i] * a.Mmax * 2;
+        unsigned bits = 0;
+        for (int j = 0; j < M; ++j) {
+            const double v0 = row[2 * j], v1 = row[2 * j + 1];
+            for (int k = 0; k < a.K; ++k)
+                if ((a.kind[k] ? v1 : v0) > a.thr[k]) bits |= 1u << k;
+        }
+        cand[i] = (unsigned char)bits;
+        tp[i] = 0u;
+    }
+    __syncthreads();
+    // ---- greedy assignment in score order: one wave per combination, lane holds targets lane, lane + 64, ... ----
+    for (int k = wave; k < a.K; k += 4) {
+        const double thr = a.thr[k];
+        const int kd = a.kind[k];
+        unsigned assigned = 0;
+        for (int i = 0; i < D; ++i) {
+            if (!((cand[i] >> k) & 1)) continue;                        // (uniform over the wave)
+            const double* row = pair + (int64_t)(unsigned)key[i] * a.Mmax * 2 + kd;
+            double bv = -1.0;
+            int bj = INT_MAX;
+            for (int t = 0; t < 4; ++t) {
+                const int j = lane + 64 * t;
+                if (j < M && !((assigned >> t) & 1)) {
+                    const double v = row[2 * j];
+                    if (v > thr && v > bv) { bv = v; bj = j; }
+                }
+            }
+            for (int o = 32; o > 0; o >>= 1) {                          // largest IoU, ties to the lower target index
+                const double ov = __shfl_xor(bv, o);
+                const int oj = __shfl_xor(bj, o);
+                if (ov > bv || (ov == bv && oj < bj)) { bv = ov; bj = oj; }
+            }
+            if (bj != INT_MAX) {
+                if (lane == (bj & 63)) assigned |= 1u << (bj >> 6);
+                if (lane == 0) atomicOr(&tp[i], 1u << k);
+            }
+        }
+    }
+    __syncthreads();
+    // ---- append: one cursor atomic per workgroup ----
+    if (tid == 0) {
+        s_base = D > 0 ? (long long)atomicAdd(a.counters + kApCursor, (unsigned long long)D) : 0;
+        if (s_nan) atomicAdd(a.counters + kApNan, (unsigned long long)s_nan);
+    }
+    if (tid < C && npos[tid]) atomicAdd(a.counters + kApNpos + tid, (unsigned long long)npos[tid]);
+    __syncthreads();
+    const long long base = s_base;
+    for (int i = tid; i < D; i += 256) {
+        const long long pos = base + i;
+        if (pos >= a.capacity) { atomicAdd(a.counters + kApOverflow, 1ull); continue; }      // (the host sizes the store: never)
+        const int q = (int)(unsigned)key[i];
+        a.records[pos] = make_int4((int)__float_as_uint(score[q]), a.first_frame + b, q | ((int)label[q] << 16), (int)tp[i]);
+    }
+}
+
+struct ApFinalArgs {
+    const int4* rec;                       // ordered by (class, score desc, frame, query)
+    const long long* class_start;          // (C + 1): records of class c are [class_start[c], class_start[c + 1])
+    const unsigned long long* counters;
+    double *ap, *npos, *tp_total;          // (C-1,K) (C-1) (C-1,K)
+    long long n;
+    int C, K, R;
+};
+
+__global__ __launch_bounds__(256) void ap_finalize_kernel(ApFinalArgs a) {
+    __shared__ unsigned long long bins[kApMaxR + 1];
+    __shared__ int wsum[4];
+    const int c = 1 + blockIdx.x / a.K, k = blockIdx.x % a.K, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long s = min(max(a.class_start[c], 0ll), a.n), e = min(max(a.class_start[c + 1], s), a.n);
+    const long long np = (long long)a.counters[kApNpos + c];
+    for (int i = tid; i <= a.R; i += 256) bins[i] = 0ull;
+    __syncthreads();
+    long long carry = 0;
+    for (long long base = s; base < e; base += 256) {
+        const long long p = base + tid;
+        const bool bit = p < e && ((a.rec[p].w >> k) & 1);
+        const unsigned long long bal = __ballot(bit);
+        if (lane == 0) wsum[wave] = __popcll(bal);
+        __syncthreads();
+        int off = 0, tot = 0;
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) off += wsum[w];
+            tot += wsum[w];
+        }
+        // only TP positions can raise a bin: an FP position has the TP count of the last TP before it and a lower precision
+        if (bit && np > 0) {
+            const long long TP = carry + off + __popcll(bal & ((2ull << lane) - 1ull));
+            long long idx = TP * a.R / np;                              // largest i with i / R <= TP / npos
+            if (idx > a.R) idx = a.R;
+            const double prec = (double)TP / (double)(p - s + 1);
+            // precisions are non-negative: their bit patterns order as integers
+            if (idx >= 1) atomicMax(&bins[idx], (unsigned long long)__double_as_longlong(prec));
+        }
+        carry += tot;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double env = 0, sum = 0;
+        for (int i = a.R; i >= 1; --i) {                                // suffix maximum
+            env = fmax(env, __longlong_as_double((long long)bins[i]));
+            bins[i] = (unsigned long long)__double_as_longlong(env);
+        }
+        for (int i = 1; i <= a.R; ++i) sum += __longlong_as_double((long long)bins[i]);
+        const int o = (c - 1) * a.K + k;
+        a.ap[o] = np > 0 ? sum / (double)a.R : __longlong_as_double(0x7ff8000000000000ll);
+        a.tp_total[o] = (double)carry;
+        if (k == 0) a.npos[c - 1] = (double)np;
+    }
+}
+
+static bool ap_sizes_ok(int B, int N, int Mmax, int C) {
+    return B > 0 && N > 0 && N <= kApMaxN && Mmax > 0 && Mmax <= kApMaxM && C >= 2 && C <= kApMaxC;
+}
+
+}  // namespace dpft
+
+using namespace dpft;
+
+extern "C" int64_t dpft_dataset_ap_scratch_bytes(int32_t B, int32_t N, int32_t Mmax) {
+    if (!(B > 0 && N > 0 && N <= kApMaxN && Mmax > 0 && Mmax <= kApMaxM)) {
+        set_error("dataset_ap_scratch_bytes: sizes out of range (N <= %d, Mmax <= %d)", kApMaxN, kApMaxM);
+        return -1;
+    }
+    return (int64_t)B * N * Mmax * 2 * (int64_t)sizeof(double);
+}
+
+extern "C" int dpft_dataset_ap_update_f32(const float* cls, const float* center, const float* size, const float* angle,
+                                          const float* gt_box, const int32_t* gt_id, const int32_t* counts,
+                                          const double* iou_thrs, const int32_t* kinds, int32_t K, const float* roi6,
+                                          float min_score, void* scratch, void* records, int64_t capacity, int64_t reserved,
+                                          int64_t* counters, int32_t first_frame, int32_t B, int32_t N, int32_t Mmax,
+                                          int32_t C, dpft_stream_t stream) {
+    DPFT_REQUIRE(cls && center && size && angle && gt_box && gt_id && counts && iou_thrs && kinds && scratch && records && counters,
+                 "dataset_ap_update: null argument");
+    DPFT_REQUIRE(ap_sizes_ok(B, N, Mmax, C), "dataset_ap_update: sizes out of range (N <= %d, Mmax <= %d, 2 <= C <= %d)", kApMaxN,
+                 kApMaxM, kApMaxC);
+    DPFT_REQUIRE(K >= 1 && K <= kApMaxK, "dataset_ap_update: 1..%d combinations, got %d", kApMaxK, K);
+    DPFT_REQUIRE(reserved >= 0 && capacity - reserved >= (int64_t)B * N,
+                 "dataset_ap_update: record store too small (capacity %lld, reserved %lld, this batch up to %lld)",
+                 (long long)capacity, (long long)reserved, (long long)B * N);
+    DPFT_REQUIRE(((uintptr_t)records & 15) == 0 && ((uintptr_t)scratch & 7) == 0 && ((uintptr_t)counters & 7) == 0,
+                 "dataset_ap_update: records need 16-byte, scratch and counters 8-byte alignment");
+    ApArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int k = 0; k < K; ++k) {
+        DPFT_REQUIRE(iou_thrs[k] > 0.0 && iou_thrs[k] < 1.0 && (kinds[k] == 0 || kinds[k] == 1),
+                     "dataset_ap_update: combination %d needs a threshold inside (0, 1) and kind 0 (bev) or 1 (3d)", k);
+        a.thr[k] = iou_thrs[k];
+        a.kind[k] = kinds[k];
+    }
+    if (roi6) {
+        for (int i = 0; i < 6; ++i) {
+            DPFT_REQUIRE(roi6[i] == roi6[i] && fabsf(roi6[i]) != INFINITY, "dataset_ap_update: roi[%d] is not finite", i);
+            a.roi[i] = roi6[i];
+        }
+        a.has_roi = 1;
+    }
+    a.cls = cls; a.center = center; a.size = size; a.angle = angle; a.gt_box = gt_box; a.gt_id = gt_id; a.counts = counts;
+    a.pair = (double*)scratch; a.records = (int4*)records; a.counters = (unsigned long long*)counters;
+    a.min_score = min_score; a.capacity = capacity; a.first_frame = first_frame;
+    a.B = B; a.N = N; a.Mmax = Mmax; a.C = C; a.K = K;
+    const int64_t total = (int64_t)B * N * Mmax;
+    hipLaunchKernelGGL(ap_pair_kernel, dim3(cdiv(total, 128)), dim3(128), 0, (hipStream_t)stream, a);
+    int rc = check_launch("dataset_ap_update pairs");
+    if (rc) return rc;
+    hipLaunchKernelGGL(ap_match_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
+    return check_launch("dataset_ap_update");
+}
+
+extern "C" int dpft_dataset_ap_finalize_f64(const void* records_sorted, int64_t n_records, const int64_t* class_start,
+                                            const int64_t* counters, int32_t C, int32_t K, int32_t R, double* ap,
+                                            double* npos, double* tp_total, dpft_stream_t stream) {
+    DPFT_REQUIRE(records_sorted && class_start && counters && ap && npos && tp_total, "dataset_ap_finalize: null argument");
+    DPFT_REQUIRE(n_records >= 0 && C >= 2 && C <= kApMaxC && K >= 1 && K <= kApMaxK && R >= 2 && R <= kApMaxR,
+                 "dataset_ap_finalize: sizes out of range (2 <= C <= %d, 1 <= K <= %d, 2 <= R <= %d)", kApMaxC, kApMaxK, kApMaxR);
+    ApFinalArgs a;
+    a.rec = (const int4*)records_sorted; a.class_start = (const long long*)class_start;
+    a.counters = (const unsigned long long*)counters; a.ap = ap; a.npos = npos; a.tp_total = tp_total;
+    a.n = n_records; a.C = C; a.K = K; a.R = R;
+    hipLaunchKernelGGL(ap_finalize_kernel, dim3((C - 1) * K), dim3(256), 0, (hipStream_t)stream, a);
+    return check_launch("dataset_ap_finalize");
+}

@@ -58,9 +58,11 @@ class DataParallelEvaluator:
     latency_reps, latency_warmup = 300, 10      # evaluator.py:110,114
 
     def __init__(self, metric: Optional[torch.nn.Module] = None, exporter: Optional[Callable] = None,
-                 device: Optional[torch.device] = None, logging: Optional[str] = None):
-        """``logging``: None, 'step' or 'epoch' (evaluator.py:24-28)."""
+                 device: Optional[torch.device] = None, logging: Optional[str] = None, dataset_ap=None):
+        """``logging``: None, 'step' or 'epoch' (evaluator.py:24-28).  ``dataset_ap``: an optional
+        ``dpft_amd.evaluation.dataset_ap.DatasetAP`` -- split-level AP_BEV / AP_3D accumulated beside the per-step metrics."""
         self.eval_fn, self.export_fn, self.logging = metric, exporter, logging
+        self.dataset_ap = dataset_ap
         self.device = torch.device(device) if device is not None else torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
         self.rank = dist.get_rank() if dist.is_initialized() else 0
         self.world = dist.get_world_size() if dist.is_initialized() else 1
@@ -71,9 +73,11 @@ class DataParallelEvaluator:
         device = torch.device(config["computing"]["device"])
         if device.type == "cuda" and device.index is None:
             device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
+        from dpft_amd.evaluation.dataset_ap import DatasetAP
         return cls(metric=build_metric(config["evaluate"]),
                    exporter=build_exporter(config["evaluate"]["exporter"]["name"], config),
-                   device=device, logging=config["train"].get("logging"))
+                   device=device, logging=config["train"].get("logging"),
+                   dataset_ap=DatasetAP.from_config(config))      # (None unless evaluate.dataset_ap is set)
 
     def __call__(self, *args, **kwargs):
         return self.evaluate(*args, **kwargs)
@@ -97,7 +101,8 @@ class DataParallelEvaluator:
         """evaluator.py:138-177 on this rank's block of the split.  ``shard_start`` = global index of the block's first sample
         (default: the loader's ``sampler.start``, else 0) -- the exporter numbers its files from it.  ``rank`` / ``world``
         default to the process group's (tests pass them to play several ranks in one process).  Returns the metric means over
-        ALL ranks' steps."""
+        ALL ranks' steps; with a ``dataset_ap`` also its split-level scalars (``AP_*``, ``mAP_*``, ``npos/*``, ``dropped_nan``),
+        which are no step means: they are computed once from all ranks' records."""
         rank = self.rank if rank is None else rank
         world = self.world if world is None else world
         if shard_start is None:
@@ -115,6 +120,8 @@ class DataParallelEvaluator:
         sums: Dict[str, torch.Tensor] = {}
         steps, seen = 0, 0
         n_steps = len(data_loader) if hasattr(data_loader, "__len__") else 0
+        if self.dataset_ap is not None:
+            self.dataset_ap.reset()
         for i, (data, labels) in enumerate(data_loader):
             labels = [self._dict_to(l) for l in labels]
             data = self._dict_to(data)
@@ -125,6 +132,8 @@ class DataParallelEvaluator:
             for k, v in metrics.items():
                 v = torch.as_tensor(v, device=self.device).detach().float().reshape(())
                 sums[k] = sums[k] + v if k in sums else v.clone()
+            if self.dataset_ap is not None:
+                self.dataset_ap.update(output, labels, shard_start + seen)
             if self.export_fn is not None and root is not None:
                 self.export_fn(output, labels, shard_start + seen, root)
             seen += len(labels)
@@ -147,6 +156,12 @@ class DataParallelEvaluator:
         scalars = {k: float(vec[j]) / total for j, k in enumerate(keys)}
         if self.logging == "epoch" and rank == 0:
             self.log_scalars(writer, scalars, epoch, "test")
+        if self.dataset_ap is not None:
+            self.dataset_ap.all_gather()                # (no-op without a process group of several ranks)
+            table = self.dataset_ap.scalars()           # unaveraged: one table of the whole split
+            if self.logging is not None and rank == 0:
+                self.log_scalars(writer, table, epoch if self.logging == "epoch" else max((epoch + 1) * n_steps - 1, 0), "test")
+            scalars.update(table)
         return scalars
 
     @torch.no_grad()

@@ -182,6 +182,9 @@ SIGNATURES = {
     "dpft_resize_bilinear_nhwc_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dpft_scale_clip_f32": (_I, [_P, _P, _L, _F, _F, _F, _F, _P]),
     "dpft_detection_metrics_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _P, _P, _I, _I, _I, _I, _P]),
+    "dpft_dataset_ap_scratch_bytes": (_L, [_I, _I, _I]),
+    "dpft_dataset_ap_update_f32": (_I, [_P] * 9 + [_I, _P, _F, _P, _P, _L, _L, _P, _I, _I, _I, _I, _I, _P]),
+    "dpft_dataset_ap_finalize_f64": (_I, [_P, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "dpft_radar_projection_scratch_floats": (_L, [_I, _I, _I, _I]),
     "dpft_export_select_f32": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
     "dpft_radar_projection_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),

@@ -173,6 +173,11 @@ class DataParallelTrainer:
         if config.get("evaluate", {}).get("metrics"):
             from dpft_amd.evaluation import build_metric
             self.eval_fn = build_metric(config["evaluate"])
+        # optional split-level AP_BEV / AP_3D of every validation epoch (evaluate.dataset_ap; evaluation/dataset_ap.py)
+        self.dataset_ap = None
+        if config.get("evaluate", {}).get("dataset_ap"):
+            from dpft_amd.evaluation.dataset_ap import DatasetAP
+            self.dataset_ap = DatasetAP.from_config(config)
         opt = dict(train["optimizer"])
         name = opt.pop("name")
         self.world = dist.get_world_size() if dist.is_initialized() else 1
@@ -572,12 +577,18 @@ class DataParallelTrainer:
         self.loss_fn.eval()
         sums: Dict[str, torch.Tensor] = {}
         n = 0
+        seen = 0
+        if self.dataset_ap is not None:
+            self.dataset_ap.reset()
         for i, (data, labels) in enumerate(data_loader):
             labels = [self._dict_to(l) for l in labels]
             data = self._dict_to(data)
             output = self.model(data)
             loss, losses = self.loss_fn(output, labels)
             metrics = self.eval_fn(output, labels) if self.eval_fn is not None else {}
+            if self.dataset_ap is not None:      # frame = rank * 2^24 + local index: only uniqueness and a fixed order matter
+                self.dataset_ap.update(output, labels, (self.rank << 24) + seen)
+                seen += len(labels)
             scalars = {f"loss_{k}": v for k, v in losses.items()}
             scalars["loss"] = loss
             scalars.update(metrics)
@@ -590,7 +601,14 @@ class DataParallelTrainer:
         means = self._rank_mean({k: v / max(n, 1) for k, v in sums.items()})
         if self.logging == "epoch" and self.rank == 0 and writer is not None:
             self._log(writer, means, epoch, "val")
-        return {k: float(v) for k, v in means.items()}
+        res = {k: float(v) for k, v in means.items()}
+        if self.dataset_ap is not None:          # one table of the whole split from all ranks' records: not a mean over ranks
+            self.dataset_ap.all_gather()
+            table = self.dataset_ap.scalars()
+            if self.logging is not None and self.rank == 0 and writer is not None:
+                self._log(writer, table, epoch if self.logging == "epoch" else max((epoch + 1) * len(data_loader) - 1, 0), "val")
+            res.update(table)
+        return res
 
     def save_checkpoint(self, path: str) -> None:
         """``torch.save(model, path)`` (trainer.py:256-258) by rank 0; every rank returns after the file exists.  The

@@ -817,6 +817,35 @@ int dpft_detection_metrics_f32(const float* cls, const float* center, const floa
                                int32_t N, int32_t Mmax, int32_t C, dpft_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Split-level AP_BEV / AP_3D accumulated on the device (dpft_amd/evaluation/dataset_ap.py states the definition).
+ * A combination k < K (1 <= K <= 8) is an IoU kind (kinds[k]: 0 bev, 1 3d) and a threshold inside (0, 1); iou_thrs,
+ * kinds and roi6 are HOST arrays (roi6 = xmin, xmax, ymin, ymax, zmin, zmax with strict inequalities, NULL = no filter).
+ * update (two launches, no read-back): pairwise fp64 IoUs into scratch (dpft_dataset_ap_scratch_bytes), then per sample
+ *   the detections (argmax class != 0, score >= min_score, centre inside the roi, score not NaN) in (score desc, query
+ *   asc) order each take the best unassigned target of their class with IoU > threshold.  Every detection appends one
+ *   16-byte record (int32 x 4: score bits, first_frame + b, query | class << 16, TP bit per combination) at a position
+ *   reserved with one atomic on counters[0]; record order is arbitrary.  counters (32 int64, zero before the first
+ *   update): [0] cursor, [1] queries dropped for a NaN score, [2] records refused for lack of capacity, [16 + c]
+ *   ground-truth count of class c.  `reserved` = host-known upper bound of the cursor (sum of B * N of earlier updates):
+ *   capacity - reserved >= B * N is required, and the kernel never writes at or past capacity.
+ *   N <= 1024, Mmax <= 256, 2 <= C <= 16.  gt_box / gt_id / counts as dpft_pack_targets_f32 writes them.
+ * finalize: records_sorted = the n_records records ordered by (class, score desc, frame asc, query asc), class_start
+ *   (C + 1 int64, device) the first record of every class.  One workgroup per (class, combination): ap (C-1,K) =
+ *   mean over r_i = i / R, i = 1..R (2 <= R <= 101), of max{precision(p) : recall(p) >= r_i} (NaN for a class without
+ *   ground truth), npos (C-1), tp_total (C-1,K); all fp64.
+ * ---------------------------------------------------------------------------------------- */
+int64_t dpft_dataset_ap_scratch_bytes(int32_t B, int32_t N, int32_t Mmax);      /* -1 + dpft_last_error() when out of range */
+int dpft_dataset_ap_update_f32(const float* cls, const float* center, const float* size, const float* angle,
+                               const float* gt_box, const int32_t* gt_id, const int32_t* counts,
+                               const double* iou_thrs, const int32_t* kinds, int32_t K, const float* roi6,
+                               float min_score, void* scratch, void* records, int64_t capacity, int64_t reserved,
+                               int64_t* counters, int32_t first_frame, int32_t B, int32_t N, int32_t Mmax,
+                               int32_t C, dpft_stream_t stream);
+int dpft_dataset_ap_finalize_f64(const void* records_sorted, int64_t n_records, const int64_t* class_start,
+                                 const int64_t* counters, int32_t C, int32_t K, int32_t R, double* ap,
+                                 double* npos, double* tp_total, dpft_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * K-Radar export selection: KRadarExporter._construct_objects
  * (src/dprt/evaluation/exporters/kradar.py:231-294) for all B samples and T <= 8 confidence thresholds at once.
  * cls (B,N,C) raw scores, center (B,N,3), size (B,N,3), angle (B,N,2)=[sin,cos]; conf_thrs is a HOST array of T

@@ -1,0 +1,135 @@
+"""Cost of the split-level AP (evaluate.dataset_ap), between device events, in one run:
+
+1. ``DatasetAP.update`` at B = 4, N = 400, C = 8, about 30 targets per sample, K = 6 combinations, beside ``Metric.forward`` on the
+   same tensors (both include their ``pack_targets`` launch and host work); and the two update launches alone
+   (``dpft_dataset_ap_update_f32`` with pre-packed targets) beside ``dpft_detection_metrics_f32`` alone.
+2. ``DatasetAP.compute()`` on about 2 * 10^5 records (wall clock: it ends with a read-back), split into its sort (torch) and the
+   finalize launch.
+
+Prints JSON lines and writes them to ``--out`` (default profiles/dataset_ap.txt).
+Usage: python tools/dataset_ap_cost.py [--reps 200] [--records 200000] [--out profiles/dataset_ap.txt]"""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--reps", type=int, default=200)
+    p.add_argument("--records", type=int, default=200000)
+    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "dataset_ap.txt"))
+    args = p.parse_args()
+    import numpy as np
+    import torch
+    import dataset_ap_ref as R                                  # the tests' seeded sample builder
+    from dpft_amd.evaluation.dataset_ap import KINDS, DatasetAP
+    from dpft_amd.evaluation.metric import Metric
+    from dpft_amd.hip.lib import lib, stream
+    from dpft_amd.training.loss import pack_targets
+
+    assert torch.cuda.is_available(), "dataset_ap_cost.py measures on the GPU; there is nothing to measure without one"
+    dev = torch.device("cuda", 0)
+    B, N, Cn = 4, 400, 8
+    rng = np.random.default_rng(0)
+    samples = [R.random_sample(rng, N, int(m), Cn) for m in rng.integers(26, 35, B)]
+    out = {k: torch.from_numpy(np.stack([s[src] for s in samples])).to(dev)
+           for k, src in (("class", "cls"), ("center", "center"), ("size", "size"), ("angle", "angle"))}
+    labels = [{k: torch.from_numpy(s[k]).to(dev) for k in ("gt_center", "gt_size", "gt_angle", "gt_class")} for s in samples]
+    ap = DatasetAP(Cn, initial_capacity=1 << 22)                # (no growth inside the timed region)
+    metric = Metric(metrics={"mAP": "mAP3D", "mGIoU": "mGIoU3D"})
+    lines = []
+
+    def emit(d):
+        lines.append(json.dumps(d))
+        print(lines[-1], flush=True)
+
+    def timed(fn):
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.reps)]
+        for _ in range(10):
+            fn()
+        torch.cuda.synchronize()
+        for a, b in ev:
+            a.record()
+            fn()
+            b.record()
+        torch.cuda.synchronize()
+        t = sorted(a.elapsed_time(b) * 1e3 for a, b in ev)
+        return {"median_us": round(statistics.median(t), 1), "min_us": round(t[0], 1), "p90_us": round(t[int(0.9 * len(t))], 1)}
+
+    frame = [0]
+
+    def update():
+        ap.update(out, labels, frame[0])
+        frame[0] += B
+
+    # the entries alone, on pre-packed targets
+    counts = [int(l["gt_class"].shape[0]) for l in labels]
+    gt_box, gt_onehot, gt_id, counts_t, Mmax = pack_targets(labels, counts, Cn, dev)
+    K = len(ap.combinations)
+    thr = (C.c_double * K)(*[t for _, t in ap.combinations])
+    kinds = (C.c_int32 * K)(*[KINDS.index(k) for k, _ in ap.combinations])
+    roi = (C.c_float * 6)(*ap.roi)
+    scratch = torch.empty(int(lib.dpft_dataset_ap_scratch_bytes(B, N, Mmax)) // 8, dtype=torch.float64, device=dev)
+    records = torch.empty((1 << 22, 4), dtype=torch.int32, device=dev)
+    counters = torch.zeros(32, dtype=torch.int64, device=dev)
+    reserved = [0]
+    t4 = [out[k].contiguous() for k in ("class", "center", "size", "angle")]
+
+    def update_alone():
+        lib.call("dpft_dataset_ap_update_f32", *[t.data_ptr() for t in t4], gt_box.data_ptr(), gt_id.data_ptr(), counts_t.data_ptr(),
+                 thr, kinds, K, roi, 0.0, scratch.data_ptr(), records.data_ptr(), records.shape[0], reserved[0], counters.data_ptr(),
+                 0, B, N, Mmax, Cn, stream())
+        reserved[0] += B * N
+
+    mscratch = torch.empty((B, N, Mmax, 2), dtype=torch.float32, device=dev)
+    mout = torch.empty((B, 2), dtype=torch.float32, device=dev)
+
+    def metric_alone():
+        lib.call("dpft_detection_metrics_f32", *[t.data_ptr() for t in t4], gt_box.data_ptr(), gt_onehot.data_ptr(),
+                 counts_t.data_ptr(), 0.5, 101, mscratch.data_ptr(), mout.data_ptr(), B, N, Mmax, Cn, stream())
+
+    update()
+    n_det = int(ap.state()["counters"][0])
+    emit({"what": "update beside Metric.forward, between device events", "device": torch.cuda.get_device_name(0), "B": B, "N": N,
+          "C": Cn, "targets": counts, "K": K, "detections_per_update": n_det, "reps": args.reps,
+          "DatasetAP.update": timed(update), "Metric.forward": timed(lambda: metric(out, labels)),
+          "dpft_dataset_ap_update_f32 alone": timed(update_alone), "dpft_detection_metrics_f32 alone": timed(metric_alone)})
+
+    # compute() on ~ --records records: the same batch under new frame numbers
+    ap.reset()
+    frame[0] = 0
+    while ap._bound < args.records * N // max(n_det // B, 1):
+        update()
+    torch.cuda.synchronize()
+    walls, parts = [], []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        st = ap.state()
+        t1 = time.perf_counter()
+        DatasetAP.sort_records(st["records"])
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        res = ap.compute()
+        t3 = time.perf_counter()
+        walls.append((t3 - t2) * 1e3)
+        parts.append(((t1 - t0) * 1e3, (t2 - t1) * 1e3))
+    n = int(ap.state()["records"].shape[0])
+    emit({"what": "compute() wall clock, ms (state read-back + sort + finalize launch + result read-back)", "records": n,
+          "compute_ms_median": round(statistics.median(walls), 2), "compute_ms_min": round(min(walls), 2),
+          "of_which_state_ms": round(statistics.median(a for a, _ in parts), 2),
+          "of_which_sort_ms": round(statistics.median(b for _, b in parts), 2),
+          "mAP_3d@0.5": res["mAP_3d@0.5"]})
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
