@@ -156,3 +156,42 @@ extern "C" int dpft_assign_loss_f32(const float* cost, const int32_t* counts_hos
     return dpft_set_loss_bwd_f32(cls, center, size, angle, gt_box, gt_onehot, match, matched, weights5, alpha, sel, dcls, dcenter,
                                  dsize, dangle, B, N, Mmax, C, stream);
 }
+
+// The same host window over L supervised outputs (deep supervision): cost (L,B,N,Mmax) on the HOST, the targets' counts (B)
+// shared by the layers; L * B assignments, one upload, the layered criterion and (a layer names gradient buffers) gradient launch.
+extern "C" int dpft_assign_loss_layers_f32(const float* cost, const int32_t* counts_host, int32_t* packed_host, int32_t* packed_dev,
+                                           const dpft_loss_layer_t* layers, int32_t L, const float* gt_box, const float* gt_onehot,
+                                           const float* weights5, float alpha, const float* sel, float* scratch, float* losses,
+                                           float* layer_totals, float* total, int32_t B, int32_t N, int32_t Mmax, int32_t C,
+                                           dpft_stream_t stream) {
+    int rc = dpft_loss_layers_check(layers, L);
+    if (rc) return rc;
+    DPFT_REQUIRE(cost && counts_host && packed_host && packed_dev && B > 0 && Mmax > 0, "assign_loss_layers: null argument");
+    int32_t tiled[DPFT_LOSS_MAX_LAYERS * 64];
+    std::vector<int32_t> tiled_big;
+    int32_t* ct = tiled;
+    if ((size_t)L * B > sizeof(tiled) / sizeof(tiled[0])) {
+        tiled_big.resize((size_t)L * B);
+        ct = tiled_big.data();
+    }
+    for (int l = 0; l < L; ++l)
+        for (int b = 0; b < B; ++b) ct[l * B + b] = counts_host[b];
+    const size_t n_match = (size_t)L * B * Mmax * 2;
+    rc = dpft_lsap_batch_f32(cost, L * B, N, Mmax, ct, packed_host, packed_host + n_match);
+    if (rc) return rc;
+    if (hipMemcpyAsync(packed_dev, packed_host, (n_match + (size_t)L * B) * sizeof(int32_t), hipMemcpyHostToDevice,
+                       (hipStream_t)stream) != hipSuccess) {
+        dpft::set_error("assign_loss_layers: upload failed");
+        return DPFT_ERR_LAUNCH;
+    }
+    const int32_t* match = packed_dev;
+    const int32_t* matched = packed_dev + n_match;
+    rc = dpft_set_loss_layers_fwd_total_f32(layers, L, gt_box, gt_onehot, match, matched, weights5, alpha, sel, scratch, losses,
+                                            layer_totals, total, B, N, Mmax, C, stream);
+    if (rc) return rc;
+    bool grads = false;
+    for (int l = 0; l < L; ++l) grads = grads || layers[l].dcls != nullptr;
+    if (!grads) return rc;
+    return dpft_set_loss_layers_bwd_f32(layers, L, gt_box, gt_onehot, match, matched, weights5, alpha, sel, nullptr, B, N, Mmax, C,
+                                        stream);
+}

@@ -229,3 +229,27 @@ extern "C" int dpft_assign_loss_dev_f32(const float* cost, const int32_t* counts
     return dpft_set_loss_bwd_f32(cls, center, size, angle, gt_box, gt_onehot, match, matched, weights5, alpha, sel, dcls, dcenter,
                                  dsize, dangle, B, N, Mmax, C, stream);
 }
+
+// The same over L supervised outputs (deep supervision): one assignment launch on L * B pseudo-samples, the layered criterion and,
+// when a layer names gradient buffers, the layered gradient.  Nothing is launched when the layer table is refused.
+extern "C" int dpft_assign_loss_layers_dev_f32(const float* cost, const int32_t* counts_tiled, int32_t* packed_dev, int32_t* status,
+                                               const dpft_loss_layer_t* layers, int32_t L, const float* gt_box,
+                                               const float* gt_onehot, const float* weights5, float alpha, const float* sel,
+                                               float* scratch, float* losses, float* layer_totals, float* total, int32_t B,
+                                               int32_t N, int32_t Mmax, int32_t C, dpft_stream_t stream) {
+    int rc = dpft_loss_layers_check(layers, L);
+    if (rc) return rc;
+    DPFT_REQUIRE(packed_dev && B > 0, "assign_loss_layers_dev: null argument");
+    int32_t* match = packed_dev;
+    int32_t* matched = packed_dev + (size_t)L * B * Mmax * 2;
+    rc = dpft_lsap_batch_dev_f32(cost, counts_tiled, match, matched, status, L * B, N, Mmax, stream);
+    if (rc) return rc;
+    rc = dpft_set_loss_layers_fwd_total_f32(layers, L, gt_box, gt_onehot, match, matched, weights5, alpha, sel, scratch, losses,
+                                            layer_totals, total, B, N, Mmax, C, stream);
+    if (rc) return rc;
+    bool grads = false;
+    for (int l = 0; l < L; ++l) grads = grads || layers[l].dcls != nullptr;
+    if (!grads) return rc;
+    return dpft_set_loss_layers_bwd_f32(layers, L, gt_box, gt_onehot, match, matched, weights5, alpha, sel, nullptr, B, N, Mmax, C,
+                                        stream);
+}

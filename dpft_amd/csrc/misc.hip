@@ -106,32 +106,77 @@ struct CostArgs {
     float w_class, w_center, w_size, w_angle, w_giou;
     int B, N, Mmax, C;
 };
-__global__ void match_cost_kernel(CostArgs a) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (int64_t)a.B * a.N * a.Mmax) return;
-    const int j = (int)(idx % a.Mmax);
-    const int64_t bn = idx / a.Mmax;
-    const int b = (int)(bn / a.N);
-    if (j >= a.counts[b]) {
-        a.cost[idx] = 0.f;
+// One (sample, query, target) entry of one supervised output -- stated once for match_cost_kernel and match_cost_layers_kernel
+// (`cost` = that output's (B,N,Mmax) matrix, idx its flat index)
+__device__ __forceinline__ void match_cost_entry(const float* __restrict__ cls, const float* __restrict__ center,
+                                                 const float* __restrict__ size, const float* __restrict__ angle,
+                                                 const float* __restrict__ gt_box, const int32_t* __restrict__ gt_id,
+                                                 const int32_t* __restrict__ counts, float* __restrict__ cost, float w_class,
+                                                 float w_center, float w_size, float w_angle, float w_giou, int64_t idx, int N,
+                                                 int Mmax, int C) {
+    const int j = (int)(idx % Mmax);
+    const int64_t bn = idx / Mmax;
+    const int b = (int)(bn / N);
+    if (j >= counts[b]) {
+        cost[idx] = 0.f;
         return;
     }
-    const float* g = a.gt_box + ((int64_t)b * a.Mmax + j) * 8;
-    const float* ce = a.center + bn * 3;
-    const float* sz = a.size + bn * 3;
-    const float* an = a.angle + bn * 2;
+    const float* g = gt_box + ((int64_t)b * Mmax + j) * 8;
+    const float* ce = center + bn * 3;
+    const float* sz = size + bn * 3;
+    const float* an = angle + bn * 2;
     const float pa[7] = {ce[0], ce[1], ce[2], sz[0], sz[1], sz[2], atan2f(an[0], an[1])};
     const float pb[7] = {g[0], g[1], g[2], g[3], g[4], g[5], atan2f(g[6], g[7])};
     const float giou = giou3d_yaw_pair(pa, pb);
     const float l1c = fabsf(ce[0] - g[0]) + fabsf(ce[1] - g[1]) + fabsf(ce[2] - g[2]);
     const float l1s = fabsf(sz[0] - g[3]) + fabsf(sz[1] - g[4]) + fabsf(sz[2] - g[5]);
     const float l1a = fabsf(an[0] - g[6]) + fabsf(an[1] - g[7]);
-    float c = a.w_class * (-a.cls[bn * a.C + a.gt_id[b * a.Mmax + j]]);
-    c += a.w_center * l1c;
-    c += a.w_size * l1s;
-    c += a.w_angle * l1a;
-    c += a.w_giou * (-giou);
-    a.cost[idx] = c;
+    float c = w_class * (-cls[bn * C + gt_id[b * Mmax + j]]);
+    c += w_center * l1c;
+    c += w_size * l1s;
+    c += w_angle * l1a;
+    c += w_giou * (-giou);
+    cost[idx] = c;
+}
+__global__ void match_cost_kernel(CostArgs a) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (int64_t)a.B * a.N * a.Mmax) return;
+    match_cost_entry(a.cls, a.center, a.size, a.angle, a.gt_box, a.gt_id, a.counts, a.cost, a.w_class, a.w_center, a.w_size,
+                     a.w_angle, a.w_giou, idx, a.N, a.Mmax, a.C);
+}
+
+// ---- deep supervision: L supervised outputs ("layers": 0 = the final decoder iteration, 1 + i = iteration i) in separate
+// allocations, named by a table of pointers that travels BY VALUE in the kernel arguments (like PackTargetsArgs below): no
+// stacking copy, no table upload.  Targets are shared: pseudo-sample s = l * B + b reads gt_*[b].
+struct LossPoint {
+    const float *cls, *center, *size, *angle;      // (B,N,C) (B,N,3) (B,N,3) (B,N,2)
+    float *dcls, *dcenter, *dsize, *dangle;        // gradients, all four or none
+};
+struct LayerTable {
+    LossPoint p[DPFT_LOSS_MAX_LAYERS];
+    float weight[DPFT_LOSS_MAX_LAYERS];
+};
+struct CostLayersArgs {
+    LayerTable t;
+    const float* gt_box;
+    const int32_t* gt_id;
+    const int32_t* counts;          // (B)
+    float* cost;                    // (L,B,N,Mmax)
+    int32_t* counts_tiled;          // (L*B): counts repeated per layer, what the assignment of L*B pseudo-samples reads
+    float w_class, w_center, w_size, w_angle, w_giou;
+    int B, N, Mmax, C;
+};
+// grid (blocks of one layer, L): entry [l] is match_cost_kernel on layer l's tensors
+__global__ void match_cost_layers_kernel(CostLayersArgs a) {
+    const int l = blockIdx.y;
+    if (blockIdx.x == 0)
+        for (int b = threadIdx.x; b < a.B; b += blockDim.x) a.counts_tiled[l * a.B + b] = a.counts[b];
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t per = (int64_t)a.B * a.N * a.Mmax;
+    if (idx >= per) return;
+    const LossPoint& p = a.t.p[l];
+    match_cost_entry(p.cls, p.center, p.size, p.angle, a.gt_box, a.gt_id, a.counts, a.cost + (int64_t)l * per, a.w_class,
+                     a.w_center, a.w_size, a.w_angle, a.w_giou, idx, a.N, a.Mmax, a.C);
 }
 
 // ---- per-step detection metrics (src/dprt/evaluation/metric.py: mAP3D :16-151, mGIoU3D :154-253) --------------------
@@ -316,90 +361,106 @@ __device__ __forceinline__ void focal_term(float x, float t, float alpha, float&
     const float sg = 1.f / (1.f + expf(-x));
     dldx = at * ((sg - t) * om * om - ce * 2.f * om * (2.f * t - 1.f));
 }
+// The criterion of one (sample, query) of one supervised output -- stated once for set_loss_kernel and the layered kernels.
+// g[k] = the factor of term k (weight / B, times the upstream gradient in the backward); match (B,Mmax,2) and counts (B) are
+// that output's assignment; part[k] += this query's share of term k; BWD writes the four gradient rows of the query.
+template <bool BWD>
+__device__ __forceinline__ void set_loss_point(const LossPoint& p, const float* __restrict__ gt_box,
+                                               const float* __restrict__ gt_onehot, const int32_t* __restrict__ match,
+                                               const int32_t* __restrict__ counts, float alpha, const float (&g)[5], int64_t bn,
+                                               int N, int Mmax, int C, float (&part)[5]) {
+    const int b = (int)(bn / N), n = (int)(bn - (int64_t)b * N);
+    const int M = counts[b];
+    int kk = -1;
+    for (int k = 0; k < M; ++k)
+        if (match[((int64_t)b * Mmax + k) * 2] == n) kk = k;
+    const int jj = kk >= 0 ? match[((int64_t)b * Mmax + kk) * 2 + 1] : -1;
+    const float* x = p.cls + bn * C;
+    const float invM = M > 0 ? 1.f / (float)M : 0.f;
+    // total_class over every query (one-hot row: background unless matched; matched rows take the kk-th target
+    // row -- assignment order, loss.py:305-306), object_class over the matched ones
+    for (int c = 0; c < C; ++c) {
+        float dl = 0.f;
+        if (M > 0) {
+            const float t = kk >= 0 ? gt_onehot[((int64_t)b * Mmax + kk) * C + c] : (c == 0 ? 1.f : 0.f);
+            float l, d;
+            focal_term(x[c], t, alpha, l, d);
+            part[0] += l * invM * g[0];
+            dl += d * invM * g[0];
+            if (kk >= 0) {
+                const float t2 = gt_onehot[((int64_t)b * Mmax + jj) * C + c];
+                focal_term(x[c], t2, alpha, l, d);
+                const float sc = (float)N * invM * invM * g[1];
+                part[1] += l * sc;
+                dl += d * sc;
+            }
+        }
+        if (BWD) p.dcls[bn * C + c] = dl;
+    }
+    const float* gb = kk >= 0 ? gt_box + ((int64_t)b * Mmax + jj) * 8 : nullptr;
+    for (int d = 0; d < 3; ++d) {
+        float dc = 0.f, ds = 0.f;
+        if (gb) {
+            const float e1 = p.center[bn * 3 + d] - gb[d], e2 = p.size[bn * 3 + d] - gb[3 + d];
+            const float s1 = invM / 3.f * g[2], s2 = invM / 3.f * g[3];
+            part[2] += fabsf(e1) * s1;
+            part[3] += fabsf(e2) * s2;
+            dc = (e1 > 0.f ? 1.f : (e1 < 0.f ? -1.f : 0.f)) * s1;
+            ds = (e2 > 0.f ? 1.f : (e2 < 0.f ? -1.f : 0.f)) * s2;
+        }
+        if (BWD) {
+            p.dcenter[bn * 3 + d] = dc;
+            p.dsize[bn * 3 + d] = ds;
+        }
+    }
+    for (int d = 0; d < 2; ++d) {
+        float da = 0.f;
+        if (gb) {
+            const float e = p.angle[bn * 2 + d] - gb[6 + d];
+            const float s = invM / 2.f * g[4];
+            part[4] += fabsf(e) * s;
+            da = (e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f)) * s;
+        }
+        if (BWD) p.dangle[bn * 2 + d] = da;
+    }
+}
+// the block's five partial sums: butterfly over each wavefront, one row of `red` per term (read after a __syncthreads as
+// red[k][0] + red[k][1] + red[k][2] + red[k][3] -- block_term)
+__device__ __forceinline__ void wave_terms(const float (&part)[5], float (&red)[5][4]) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        float v = part[k];
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
+        if (lane == 0) red[k][wv] = v;
+    }
+}
+__device__ __forceinline__ float block_term(const float (&red)[5][4], int k) { return red[k][0] + red[k][1] + red[k][2] + red[k][3]; }
+
 template <bool BWD>
 __global__ __launch_bounds__(256) void set_loss_kernel(LossArgs a) {
     __shared__ float red[5][4];
     const int64_t bn = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     float part[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     if (bn < (int64_t)a.B * a.N) {
-        const int b = (int)(bn / a.N), n = (int)(bn - (int64_t)b * a.N);
-        const int M = a.counts[b];
-        const int C = a.C;
         float g[5];
 #pragma unroll
         for (int k = 0; k < 5; ++k) g[k] = BWD ? a.gout[k] * a.w[k] / (float)a.B : a.w[k] / (float)a.B;
-        int kk = -1;
-        for (int k = 0; k < M; ++k)
-            if (a.match[((int64_t)b * a.Mmax + k) * 2] == n) kk = k;
-        const int jj = kk >= 0 ? a.match[((int64_t)b * a.Mmax + kk) * 2 + 1] : -1;
-        const float* x = a.cls + bn * C;
-        const float invM = M > 0 ? 1.f / (float)M : 0.f;
-        // total_class over every query (one-hot row: background unless matched; matched rows take the kk-th target
-        // row -- assignment order, loss.py:305-306), object_class over the matched ones
-        for (int c = 0; c < C; ++c) {
-            float dl = 0.f;
-            if (M > 0) {
-                const float t = kk >= 0 ? a.gt_onehot[((int64_t)b * a.Mmax + kk) * C + c] : (c == 0 ? 1.f : 0.f);
-                float l, d;
-                focal_term(x[c], t, a.alpha, l, d);
-                part[0] += l * invM * g[0];
-                dl += d * invM * g[0];
-                if (kk >= 0) {
-                    const float t2 = a.gt_onehot[((int64_t)b * a.Mmax + jj) * C + c];
-                    focal_term(x[c], t2, a.alpha, l, d);
-                    const float sc = (float)a.N * invM * invM * g[1];
-                    part[1] += l * sc;
-                    dl += d * sc;
-                }
-            }
-            if (BWD) a.dcls[bn * C + c] = dl;
-        }
-        const float* gb = kk >= 0 ? a.gt_box + ((int64_t)b * a.Mmax + jj) * 8 : nullptr;
-        for (int d = 0; d < 3; ++d) {
-            float dc = 0.f, ds = 0.f;
-            if (gb) {
-                const float e1 = a.center[bn * 3 + d] - gb[d], e2 = a.size[bn * 3 + d] - gb[3 + d];
-                const float s1 = invM / 3.f * g[2], s2 = invM / 3.f * g[3];
-                part[2] += fabsf(e1) * s1;
-                part[3] += fabsf(e2) * s2;
-                dc = (e1 > 0.f ? 1.f : (e1 < 0.f ? -1.f : 0.f)) * s1;
-                ds = (e2 > 0.f ? 1.f : (e2 < 0.f ? -1.f : 0.f)) * s2;
-            }
-            if (BWD) {
-                a.dcenter[bn * 3 + d] = dc;
-                a.dsize[bn * 3 + d] = ds;
-            }
-        }
-        for (int d = 0; d < 2; ++d) {
-            float da = 0.f;
-            if (gb) {
-                const float e = a.angle[bn * 2 + d] - gb[6 + d];
-                const float s = invM / 2.f * g[4];
-                part[4] += fabsf(e) * s;
-                da = (e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f)) * s;
-            }
-            if (BWD) a.dangle[bn * 2 + d] = da;
-        }
+        const LossPoint p{a.cls, a.center, a.size, a.angle, a.dcls, a.dcenter, a.dsize, a.dangle};
+        set_loss_point<BWD>(p, a.gt_box, a.gt_onehot, a.match, a.counts, a.alpha, g, bn, a.N, a.Mmax, a.C, part);
     }
     if (!BWD) {
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            float v = part[k];
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-            if (lane == 0) red[k][wv] = v;
-        }
+        wave_terms(part, red);
         __syncthreads();
         if (a.slab == nullptr) {
-            if (threadIdx.x < 5) atomicAdd(a.losses + threadIdx.x, red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3]);
+            if (threadIdx.x < 5) atomicAdd(a.losses + threadIdx.x, block_term(red, threadIdx.x));
             return;
         }
         __shared__ int last;
         __shared__ float tot[5];
         if (threadIdx.x < 5)
-            __hip_atomic_store(a.slab + 8 + (size_t)blockIdx.x * 8 + threadIdx.x,
-                               red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3], __ATOMIC_RELAXED,
+            __hip_atomic_store(a.slab + 8 + (size_t)blockIdx.x * 8 + threadIdx.x, block_term(red, threadIdx.x), __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -418,6 +479,93 @@ __global__ __launch_bounds__(256) void set_loss_kernel(LossArgs a) {
         __syncthreads();
         if (threadIdx.x == 0 && a.total) *a.total = tot[0] + tot[1] + tot[2] + tot[3] + tot[4];
     }
+}
+
+// ---- the criterion over L supervised outputs: grid (blocks of one layer, L), so no block straddles two layers ----
+struct LossLayersArgs {
+    LayerTable t;
+    const float* gt_box;        // (B,Mmax,8)    shared by the layers
+    const float* gt_onehot;     // (B,Mmax,C)
+    const int32_t* match;       // (L,B,Mmax,2)
+    const int32_t* counts;      // (L,B) matched counts
+    const float* sel;           // (5)
+    const float* gout;          // device scalar or null (= 1)                                       (backward)
+    float* slab;                // [ticket (8 floats)][L][blocks][8]                                 (forward)
+    float* losses;              // (L,5) the weighted batch-mean terms of every layer, WITHOUT the layer weight
+    float* layer_totals;        // (L)   weight_l * sum_k sel[k] * losses[l,k]
+    float* total;               // their sum in layer order
+    float w[5];
+    float alpha;
+    int B, N, Mmax, C, L;
+};
+__global__ __launch_bounds__(256) void set_loss_layers_fwd_kernel(LossLayersArgs a) {
+    __shared__ float red[5][4];
+    const int l = blockIdx.y;
+    const int64_t bn = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    float part[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    if (bn < (int64_t)a.B * a.N) {
+        float g[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) g[k] = a.w[k] / (float)a.B;
+        set_loss_point<false>(a.t.p[l], a.gt_box, a.gt_onehot, a.match + (int64_t)l * a.B * a.Mmax * 2, a.counts + l * a.B, a.alpha,
+                              g, bn, a.N, a.Mmax, a.C, part);
+    }
+    wave_terms(part, red);
+    __syncthreads();
+    __shared__ int last;
+    __shared__ float tot[DPFT_LOSS_MAX_LAYERS][5];
+    __shared__ float lt[DPFT_LOSS_MAX_LAYERS];
+    const int nbx = (int)gridDim.x;
+    if (threadIdx.x < 5)
+        __hip_atomic_store(a.slab + 8 + ((size_t)l * nbx + blockIdx.x) * 8 + threadIdx.x, block_term(red, threadIdx.x),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    int* ticket = reinterpret_cast<int*>(a.slab);
+    if (threadIdx.x == 0)
+        last = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nbx * (int)gridDim.y - 1;
+    __syncthreads();
+    if (!last) return;
+    if (threadIdx.x == 0) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // left clean
+    if ((int)threadIdx.x < 5 * a.L) {
+        const int ll = threadIdx.x / 5, k = threadIdx.x - ll * 5;
+        float t = 0.f;
+        for (int b = 0; b < nbx; ++b) {    // block order, as set_loss_kernel adds one output's partial sums
+            float* s = a.slab + 8 + ((size_t)ll * nbx + b) * 8 + k;
+            t += __hip_atomic_load(s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(s, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // the whole scratch is left zero
+        }
+        a.losses[ll * 5 + k] = t;
+        tot[ll][k] = t * a.sel[k];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < a.L) {
+        const int ll = threadIdx.x;
+        const float v = a.t.weight[ll] * (tot[ll][0] + tot[ll][1] + tot[ll][2] + tot[ll][3] + tot[ll][4]);
+        a.layer_totals[ll] = v;
+        lt[ll] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = lt[0];
+        for (int ll = 1; ll < a.L; ++ll) t += lt[ll];
+        *a.total = t;
+    }
+}
+// d total / d (cls, center, size, angle) of every layer that has gradient pointers, the factor of term k being
+// (weight_l * gout * sel[k]) * w[k] / B -- set_loss_kernel<true> with gout5 = (weight_l * gout) * sel
+__global__ __launch_bounds__(256) void set_loss_layers_bwd_kernel(LossLayersArgs a) {
+    const int l = blockIdx.y;
+    const LossPoint& p = a.t.p[l];
+    if (p.dcls == nullptr) return;
+    const int64_t bn = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (bn >= (int64_t)a.B * a.N) return;
+    const float wl = a.gout ? a.t.weight[l] * a.gout[0] : a.t.weight[l];
+    float g[5], part[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 5; ++k) g[k] = (wl * a.sel[k]) * a.w[k] / (float)a.B;
+    set_loss_point<true>(p, a.gt_box, a.gt_onehot, a.match + (int64_t)l * a.B * a.Mmax * 2, a.counts + l * a.B, a.alpha, g, bn,
+                         a.N, a.Mmax, a.C, part);
 }
 
 }  // namespace dpft
@@ -562,6 +710,96 @@ extern "C" int dpft_set_loss_bwd_f32(const float* cls, const float* center, cons
     a.gout = gout5; a.dcls = dcls; a.dcenter = dcenter; a.dsize = dsize; a.dangle = dangle;
     hipLaunchKernelGGL(set_loss_kernel<true>, dim3(cdiv((int64_t)B * N, 256)), dim3(256), 0, (hipStream_t)stream, a);
     return check_launch("set_loss_bwd");
+}
+
+// ---- deep supervision: the matcher cost, the criterion and its gradient over L supervised outputs, one launch each ----
+extern "C" int dpft_loss_layers_check(const dpft_loss_layer_t* layers, int32_t L) {
+    DPFT_REQUIRE(L >= 1 && L <= DPFT_LOSS_MAX_LAYERS, "loss_layers: %d layers, expected 1..%d", L, DPFT_LOSS_MAX_LAYERS);
+    DPFT_REQUIRE(layers, "loss_layers: null layer table");
+    for (int l = 0; l < L; ++l) {
+        const dpft_loss_layer_t& y = layers[l];
+        DPFT_REQUIRE(y.cls && y.center && y.size && y.angle, "loss_layers: layer %d has a null output", l);
+        const int ng = (y.dcls != nullptr) + (y.dcenter != nullptr) + (y.dsize != nullptr) + (y.dangle != nullptr);
+        DPFT_REQUIRE(ng == 0 || ng == 4, "loss_layers: layer %d names %d of its 4 gradient buffers (all or none)", l, ng);
+        DPFT_REQUIRE(std::isfinite(y.weight) && y.weight >= 0.f, "loss_layers: layer %d has weight %g (finite and >= 0 expected)", l,
+                     (double)y.weight);
+    }
+    return DPFT_OK;
+}
+
+static int layers_fill(LayerTable& t, const dpft_loss_layer_t* layers, int L) {
+    const int rc = dpft_loss_layers_check(layers, L);
+    if (rc) return rc;
+    memset(&t, 0, sizeof(t));
+    for (int l = 0; l < L; ++l) {
+        const dpft_loss_layer_t& y = layers[l];
+        t.p[l] = LossPoint{y.cls, y.center, y.size, y.angle, y.dcls, y.dcenter, y.dsize, y.dangle};
+        t.weight[l] = y.weight;
+    }
+    return DPFT_OK;
+}
+
+extern "C" int dpft_match_cost_layers_f32(const dpft_loss_layer_t* layers, int32_t L, const float* gt_box, const int32_t* gt_id,
+                                          const int32_t* counts, const float* weights5, float* cost, int32_t* counts_tiled,
+                                          int32_t B, int32_t N, int32_t Mmax, int32_t C, dpft_stream_t stream) {
+    CostLayersArgs a;
+    int rc = layers_fill(a.t, layers, L);
+    if (rc) return rc;
+    DPFT_REQUIRE(gt_box && gt_id && counts && weights5 && cost && counts_tiled, "match_cost_layers: null argument");
+    DPFT_REQUIRE(B > 0 && N > 0 && Mmax > 0 && C > 0, "match_cost_layers: non-positive sizes");
+    a.gt_box = gt_box; a.gt_id = gt_id; a.counts = counts; a.cost = cost; a.counts_tiled = counts_tiled;
+    a.w_class = weights5[0]; a.w_center = weights5[1]; a.w_size = weights5[2]; a.w_angle = weights5[3]; a.w_giou = weights5[4];
+    a.B = B; a.N = N; a.Mmax = Mmax; a.C = C;
+    const int64_t per = (int64_t)B * N * Mmax;
+    hipLaunchKernelGGL(match_cost_layers_kernel, dim3(cdiv(per, 128), L), dim3(128), 0, (hipStream_t)stream, a);
+    return check_launch("match_cost_layers");
+}
+
+static int loss_layers_fill(LossLayersArgs& a, const dpft_loss_layer_t* layers, int L, const float* gt_box, const float* gt_onehot,
+                            const int32_t* match, const int32_t* counts, const float* weights5, float alpha, const float* sel,
+                            int B, int N, int Mmax, int C) {
+    memset(&a, 0, sizeof(a));
+    int rc = layers_fill(a.t, layers, L);
+    if (rc) return rc;
+    DPFT_REQUIRE(gt_box && gt_onehot && match && counts && weights5 && sel, "set_loss_layers: null argument");
+    DPFT_REQUIRE(B > 0 && N > 0 && Mmax > 0 && C > 0, "set_loss_layers: non-positive sizes");
+    a.gt_box = gt_box; a.gt_onehot = gt_onehot; a.match = match; a.counts = counts; a.sel = sel; a.alpha = alpha;
+    a.B = B; a.N = N; a.Mmax = Mmax; a.C = C; a.L = L;
+    for (int k = 0; k < 5; ++k) a.w[k] = weights5[k];
+    return DPFT_OK;
+}
+
+extern "C" int64_t dpft_set_loss_layers_scratch_floats(int32_t L, int32_t B, int32_t N) {
+    return 8 + 8 * (int64_t)(L > 0 ? L : 0) * cdiv((int64_t)B * N, 256);
+}
+
+extern "C" int dpft_set_loss_layers_fwd_total_f32(const dpft_loss_layer_t* layers, int32_t L, const float* gt_box,
+                                                  const float* gt_onehot, const int32_t* match, const int32_t* counts,
+                                                  const float* weights5, float alpha, const float* sel, float* scratch,
+                                                  float* losses, float* layer_totals, float* total, int32_t B, int32_t N,
+                                                  int32_t Mmax, int32_t C, dpft_stream_t stream) {
+    LossLayersArgs a;
+    int rc = loss_layers_fill(a, layers, L, gt_box, gt_onehot, match, counts, weights5, alpha, sel, B, N, Mmax, C);
+    if (rc) return rc;
+    DPFT_REQUIRE(scratch && losses && layer_totals && total, "set_loss_layers_fwd_total: null tensor");
+    a.slab = scratch; a.losses = losses; a.layer_totals = layer_totals; a.total = total;
+    hipLaunchKernelGGL(set_loss_layers_fwd_kernel, dim3(cdiv((int64_t)B * N, 256), L), dim3(256), 0, (hipStream_t)stream, a);
+    return check_launch("set_loss_layers_fwd_total");
+}
+
+extern "C" int dpft_set_loss_layers_bwd_f32(const dpft_loss_layer_t* layers, int32_t L, const float* gt_box, const float* gt_onehot,
+                                            const int32_t* match, const int32_t* counts, const float* weights5, float alpha,
+                                            const float* sel, const float* gout, int32_t B, int32_t N, int32_t Mmax, int32_t C,
+                                            dpft_stream_t stream) {
+    LossLayersArgs a;
+    int rc = loss_layers_fill(a, layers, L, gt_box, gt_onehot, match, counts, weights5, alpha, sel, B, N, Mmax, C);
+    if (rc) return rc;
+    bool any = false;
+    for (int l = 0; l < L; ++l) any = any || layers[l].dcls != nullptr;
+    DPFT_REQUIRE(any, "set_loss_layers_bwd: no layer names gradient buffers");
+    a.gout = gout;
+    hipLaunchKernelGGL(set_loss_layers_bwd_kernel, dim3(cdiv((int64_t)B * N, 256), L), dim3(256), 0, (hipStream_t)stream, a);
+    return check_launch("set_loss_layers_bwd");
 }
 
 extern "C" int dpft_detection_metrics_f32(const float* cls, const float* center, const float* size, const float* angle,

@@ -86,6 +86,15 @@ class OuterSpec(C.Structure):
     _fields_ = [("col_a", C.c_int32), ("n_a", C.c_int32), ("col_b", C.c_int32), ("n_b", C.c_int32), ("out_off", C.c_int64)]
 
 
+class LossLayer(C.Structure):
+    """dpft_loss_layer_t: one supervised output of the layered loss entries (deep supervision)."""
+    _fields_ = [("cls", C.c_void_p), ("center", C.c_void_p), ("size", C.c_void_p), ("angle", C.c_void_p),
+                ("dcls", C.c_void_p), ("dcenter", C.c_void_p), ("dsize", C.c_void_p), ("dangle", C.c_void_p),
+                ("weight", C.c_float)]
+
+
+LOSS_MAX_LAYERS = 8      # DPFT_LOSS_MAX_LAYERS
+
 _P, _I, _L, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 _DESC = C.POINTER(ConvDesc)
 _PYR = C.POINTER(Pyramid)
@@ -196,6 +205,13 @@ SIGNATURES = {
     "dpft_profile_get_family": (_I, [_I, C.POINTER(_I)]),
     "dpft_rows_outer_f32": (_I, [_P, _I, _I, _I, _P, _I, _P, _L, _P]),
     "dpft_memops": (_I, [_I, _P, _P]),
+    "dpft_loss_layers_check": (_I, [_P, _I]),
+    "dpft_match_cost_layers_f32": (_I, [_P, _I, _P, _P, _P, C.POINTER(_F * 5), _P, _P, _I, _I, _I, _I, _P]),
+    "dpft_set_loss_layers_scratch_floats": (_L, [_I, _I, _I]),
+    "dpft_set_loss_layers_fwd_total_f32": (_I, [_P, _I, _P, _P, _P, _P, C.POINTER(_F * 5), _F, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "dpft_set_loss_layers_bwd_f32": (_I, [_P, _I, _P, _P, _P, _P, C.POINTER(_F * 5), _F, _P, _P, _I, _I, _I, _I, _P]),
+    "dpft_assign_loss_layers_dev_f32": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "dpft_assign_loss_layers_f32": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "dpft_lsap_batch_f32": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "dpft_assign_loss_f32": (_I, [_P] * 11 + [_F] + [_P] * 8 + [_I] * 4 + [_P]),
     "dpft_lsap_batch_dev_f32": (_I, [_P] * 5 + [_I] * 3 + [_P]),

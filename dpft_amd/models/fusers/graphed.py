@@ -44,7 +44,12 @@ class _FlatFuser(nn.Module):
         proj = [(next(it), next(it)) for _ in range(n)]
         out = self.fuser(batch=views, shape=shapes, projection=proj, out=OrderedDict(center=center0),
                          has_transformation=self.flags)
-        return out["center"], out["size"], out["angle"], out["class"]
+        # deep supervision (fuser.return_aux): the final iteration's four first -- outputs [:4] keep their meaning --, then
+        # iterations 0 .. I-2, four tensors each
+        flat = [out["center"], out["size"], out["angle"], out["class"]]
+        for o in out.get("aux_outputs", ()):
+            flat += [o["center"], o["size"], o["angle"], o["class"]]
+        return tuple(flat)
 
 
 class _Replay(torch.autograd.Function):
@@ -102,7 +107,8 @@ class GraphedFuser:
 
     def backward_from(self, write_output_grads) -> None:
         """The backward of the replayed decoder WITHOUT the autograd engine in front of it: ``write_output_grads`` fills
-        ``static_grad_outputs`` (center, size, angle, class) in place, the backward graph is launched at once, and only
+        ``static_grad_outputs`` (center, size, angle, class of the final iteration; with ``return_aux`` those of iterations
+        0 .. I-2 behind them) in place, the backward graph is launched at once, and only
         then autograd is started on the pyramid tensors (and a learned querent's centres) with the graph's input gradients --
         the engine's start-up (~0.2 ms on the host, after the step's host sync, with an idle GPU) hides behind the decoder's
         backward."""
@@ -123,6 +129,7 @@ class GraphedFuser:
     def __init__(self, model: nn.Module, sample_batch: Dict[str, torch.Tensor], warmup: int = 3, grad_direct=None):
         self.inputs = list(model.inputs)
         self.grad_direct = grad_direct
+        self.return_aux = bool(getattr(model.fuser, "return_aux", False))      # read here: the graphs are recorded with it
         was_training = model.training
         # one eval-mode pass up to the fuser (no running-stat update, no autograd) for correctly shaped samples
         model.eval()
@@ -226,11 +233,18 @@ class GraphedFuser:
             args += [t, p]
         if [tuple(a.shape) for a in args] != self.shapes:
             raise RuntimeError("graphed fuser called with shapes different from the captured ones")
+        if bool(getattr(self.flat.fuser, "return_aux", False)) != self.return_aux:
+            raise RuntimeError(f"graphed fuser: fuser.return_aux was {self.return_aux} at capture and has been changed since; "
+                               "call enable_graphs / enable_fuser_graph again to record the decoder with the new setting")
         if not torch.is_grad_enabled():
             ops.memops(list(zip(self.eval_inputs, args)))
             self.eval_graph.replay()
             c, s, a, k = (o.clone() for o in self.eval_outputs)
             return OrderedDict([("center", c), ("size", s), ("angle", a), ("class", k)])
         # parameters are passed so that autograd routes their gradients (their values are read in place)
-        c, s, a, k = _Replay.apply(self, *args, *self.params)
-        return OrderedDict([("center", c), ("size", s), ("angle", a), ("class", k)])
+        flat = _Replay.apply(self, *args, *self.params)
+        keys = ("center", "size", "angle", "class")
+        out = OrderedDict(zip(keys, flat[:4]))
+        if self.return_aux:
+            out["aux_outputs"] = [OrderedDict(zip(keys, flat[i:i + 4])) for i in range(4, len(flat), 4)]
+        return out

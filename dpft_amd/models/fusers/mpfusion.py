@@ -180,6 +180,10 @@ class IMPFusion(nn.Module):
 
     use_fused_inference = True       # eval + no_grad forward runs the fused HIP decoder when the config allows
     use_fused_train = True           # CUDA: layers run from the fused HIP training kernels when the config allows
+    # Deep supervision (train.aux_loss): with it on, a training / grad-mode forward also returns the head outputs of iterations
+    # 0 .. I-2 under "aux_outputs" (a list of OrderedDict(center, size, angle, class), iteration 0 first).  An attribute the
+    # trainer sets, not a constructor or config argument: the reference's model configs stay loadable unchanged.
+    return_aux = False
 
     def reset_parameters(self) -> None:
         self.q_init(self.query)
@@ -232,6 +236,7 @@ class IMPFusion(nn.Module):
                 # would stall the host until every encoder has finished: 4 ms of the forward latency)
                 return fused(batch, shape, projection, out, has_transformation)
         flags = has_transformation if has_transformation is not None else self.transformation_flags(projection)
+        aux = [] if self.return_aux and (self.training or torch.is_grad_enabled()) else None
         pyramids = [make_pyramid_state(list(levels.values())) for levels in batch]
         seed = None
         if self.query.is_cuda:
@@ -256,7 +261,9 @@ class IMPFusion(nn.Module):
                 for it, (layer, head) in enumerate(zip(layers, self.heads)):
                     y3 = layer.forward_fused_blocks(query, pyramids, refs, pos_hub, seed, it, batch=B)
                     query, out, refs = _tf.head_block(layer, head, proj, y3, out["center"], it + 1 < len(layers))
-                return out
+                    if aux is not None and it + 1 < len(layers):
+                        aux.append(out)
+                return self._with_aux(out, aux)
         query = self.query.unsqueeze(0).repeat(B, 1, 1)
         query_pos = self.query_embedding.weight.unsqueeze(0).repeat(B, 1, 1)
         for it, (layer, head) in enumerate(zip(self.mpfusion.values(), self.heads)):
@@ -266,7 +273,18 @@ class IMPFusion(nn.Module):
             query = layer(query, pyramids, reference_points, query_pos, pos2d=self.query_embedding.weight,
                           seed=seed, salt=it)
             out = head(query, out)
-        return out
+            if aux is not None and it + 1 < self.i_iter:
+                aux.append(out)
+        return self._with_aux(out, aux)
+
+    @staticmethod
+    def _with_aux(out, aux):
+        """The final iteration's outputs, plus "aux_outputs" = the earlier iterations' when ``return_aux`` asked for them."""
+        if aux is None:
+            return out
+        final = type(out)(out)
+        final["aux_outputs"] = [type(o)((k, o[k]) for k in ("center", "size", "angle", "class")) for o in aux]
+        return final
 
 
 def build_mpfusion(*args, **kwargs):

@@ -13,6 +13,9 @@ B per-sample ``C.cpu()`` syncs (assigner.py:135) are one padded device->host cop
 One addition the reference cannot offer (its GIoULoss, loss.py:111-173, needs pytorch3d and has no backward): the optional
 ``loss_weights["giou"]`` term, a differentiable GIoU3D over the matched pairs (``_GiouLossFn``, csrc/giou_loss.hip); off by
 default, and with the key absent nothing here runs differently.
+A second one: deep supervision (``Loss.aux_weights``, train.aux_loss) -- every intermediate decoder iteration matched and supervised
+on its own, all of them in the four launches of one output (``forward_fused_layers``, dpft_*_layers_f32 in csrc/misc.hip); off by
+default, fused path only, the GIoU term stays on the final output.
 """
 from __future__ import annotations
 
@@ -297,6 +300,49 @@ class _GiouLossFn(torch.autograd.Function):
         return dcenter, dsize, dangle, gtotal, None, None, None, None, None
 
 
+def _layer_table(tens, weights, grads=None):
+    """ctypes array of dpft_loss_layer_t: tens[l] = (cls, center, size, angle), grads[l] = (dcls, dcenter, dsize, dangle) | None."""
+    from dpft_amd.hip.lib import LossLayer
+    table = (LossLayer * len(tens))()
+    for l, (t, w) in enumerate(zip(tens, weights)):
+        e = table[l]
+        e.cls, e.center, e.size, e.angle = (x.data_ptr() for x in t)
+        if grads is not None and grads[l] is not None:
+            e.dcls, e.dcenter, e.dsize, e.dangle = (x.data_ptr() for x in grads[l])
+        e.weight = w
+    return table
+
+
+class _SetLossLayersFn(torch.autograd.Function):
+    """The criterion over several supervised outputs (deep supervision): one Function over all layers' tensors, the values
+    come from dpft_assign_loss_layers*_f32, the backward is the one dpft_set_loss_layers_bwd_f32 launch."""
+
+    @staticmethod
+    def forward(ctx, meta, pre, *flat):
+        # flat = (cls, center, size, angle) of layer 0, layer 1, ...; pre = (losses (L,5), layer_totals (L), total)
+        losses, layer_totals, total = pre
+        ctx.meta = meta
+        ctx.save_for_backward(*flat)
+        ctx.mark_non_differentiable(losses, layer_totals)
+        return losses, layer_totals, total
+
+    @staticmethod
+    def backward(ctx, _gl, _gt, gtotal):
+        import ctypes as C
+        from dpft_amd.hip.lib import lib, stream
+        layer_w, gt_box, gt_onehot, match, counts, weights5, alpha, sel = ctx.meta
+        flat = ctx.saved_tensors
+        tens = [flat[i:i + 4] for i in range(0, len(flat), 4)]
+        grads = [tuple(torch.empty_like(t) for t in tl) for tl in tens]
+        B, N, ncls = tens[0][0].shape
+        w = (C.c_float * 5)(*weights5)
+        gout = gtotal.contiguous().float()
+        table = _layer_table(tens, layer_w, grads)
+        lib.call("dpft_set_loss_layers_bwd_f32", table, len(tens), gt_box.data_ptr(), gt_onehot.data_ptr(), match.data_ptr(),
+                 counts.data_ptr(), C.byref(w), alpha, sel.data_ptr(), gout.data_ptr(), B, N, gt_box.shape[1], ncls, stream())
+        return (None, None) + tuple(g for gl in grads for g in gl)
+
+
 class Loss(nn.modules.loss._Loss):
     def __init__(self, anassigner: nn.Module = None, criterion: nn.Module = None, loss_weights: Dict[str, float] = None,
                  reduction: str = "mean", **kwargs):
@@ -337,6 +383,12 @@ class Loss(nn.modules.loss._Loss):
     # trainer switches it on and calls check_assignment_status() where it reads values back anyway (logging, epoch end).
     assign_on_device = False
 
+    # Deep supervision (train.aux_loss), off by default: None, or one finite weight >= 0 per intermediate decoder iteration.  With
+    # it set and "aux_outputs" in the inputs (IMPFusion.return_aux) every iteration is matched and supervised on its own: layer 0 =
+    # the final output with weight 1, layer 1 + i = aux_outputs[i] with aux_weights[i] -- all of them from the four launches of one
+    # output (forward_fused_layers).  The optional GIoU term stays on the final output.
+    aux_weights = None
+
     def _status_word(self, dev) -> torch.Tensor:
         """One page-locked int32 the assignment kernel writes its error code to (device-visible host memory: the host can look at it
         without a sync; it only ever changes on an error)."""
@@ -359,16 +411,28 @@ class Loss(nn.modules.loss._Loss):
         return code
 
     @staticmethod
-    def describe_assignment_status(code: int) -> str:
+    def describe_assignment_status(code: int, batch: int = None, layers=None) -> str:
+        """``batch`` (and ``layers``: which supervised output each launched layer was, 0 = the final one, 1 + i = iteration i)
+        decode the pseudo-sample index l * B + b of a deep-supervision step; without ``batch`` the index is a sample."""
         what = "contains invalid numeric entries" if code < 0x10000 else ("is infeasible" if code < 0x20000 else
                                                                           "has more targets than the packed width")
-        return f"matcher: cost matrix of sample {(code & 0xffff) - (1 if code < 0x10000 else 0)} {what}"
+        s = (code & 0xffff) - (1 if code < 0x10000 else 0)
+        if not batch:
+            return f"matcher: cost matrix of sample {s} {what}"
+        l, b = divmod(s, int(batch))
+        out = layers[l] if layers is not None and l < len(layers) else l
+        name = "the final output" if out == 0 else f"iteration {out - 1}"
+        return f"matcher: cost matrix of sample {b} of {name} {what}"
+
+    def status_decoding(self):
+        """(batch, layers) of the last deep-supervision forward for ``describe_assignment_status``, () otherwise."""
+        return self.__dict__.get("_status_layers") or ()
 
     def check_assignment_status(self, sync: bool = True) -> None:
         """Raise the ValueError scipy would have raised in the step whose cost matrix was not finite (or infeasible)."""
         code = self.assignment_status(sync)
         if code:
-            raise ValueError(self.describe_assignment_status(code))
+            raise ValueError(self.describe_assignment_status(code, *self.status_decoding()))
 
     def _to_host(self, t: torch.Tensor) -> "np.ndarray":
         """Device tensor -> numpy through a reused pinned buffer (one async copy + one stream sync instead of a pageable
@@ -507,6 +571,126 @@ class Loss(nn.modules.loss._Loss):
         self.__dict__["_last"] = (cls, center, size, angle, gt_box, gt_onehot, match_t, counts_m, weights5, 0.75, sel, total)
         return total, self._batch_losses(losses5, giou)
 
+    def _checked_aux_weights(self, n_aux: int) -> List[float]:
+        w = self.aux_weights
+        if not isinstance(w, (list, tuple)) or len(w) != n_aux or any(
+                isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or x < 0 for x in w):
+            raise ValueError(f"aux_weights must be a list of {n_aux} finite numbers >= 0 (one per intermediate decoder iteration), "
+                             f"got {w!r}")
+        return [float(x) for x in w]
+
+    def forward_fused_layers(self, inputs, aux, targets):
+        """Deep supervision: the final output (layer 0, weight 1) and every intermediate iteration with a positive weight, each
+        with its own assignment, from the four launches of ``forward_fused``: layered cost -> one C call (assignment of L * B
+        pseudo-samples, criterion, gradient into named buffers).  -> (total, {today's keys: layer 0's terms, aux_i: weighted total
+        of iteration i})."""
+        import ctypes as C
+        from dpft_amd.hip.lib import lib, stream, LOSS_MAX_LAYERS
+        aux_w = self._checked_aux_weights(len(aux))
+        if os.environ.get("DPFT_LSAP_C", "1") == "0":
+            raise ValueError("aux_weights: the DPFT_LSAP_C=0 scipy switch does not exist for deep supervision")
+        groups = [0] + [1 + i for i, w in enumerate(aux_w) if w > 0]          # supervised output of every launched layer
+        layer_w = [1.0] + [w for w in aux_w if w > 0]
+        L = len(groups)
+        if L > LOSS_MAX_LAYERS:
+            raise ValueError(f"aux_weights: {L} supervised outputs, at most {LOSS_MAX_LAYERS} per launch")
+        outs = [inputs] + [aux[g - 1] for g in groups[1:]]
+        tens = [tuple(o[k].contiguous() for k in ("class", "center", "size", "angle")) for o in outs]
+        cls, center, size, angle = tens[0]
+        B, N, ncls = cls.shape
+        dev = cls.device
+        counts = [int(t["gt_class"].shape[0]) if all(v.numel() for v in t.values()) else 0 for t in targets]
+        self.__dict__["last_has_targets"] = max(counts) > 0
+        aux_keys = [f"aux_{i}" for i in range(len(aux))]
+        if max(counts) == 0:
+            zero = torch.zeros((), device=dev, dtype=cls.dtype, requires_grad=True)
+            return zero * 1.0, {k: zero for k in list(self.loss_weights) + aux_keys}
+        gt_box, gt_onehot, gt_id, counts_t, Mmax = pack_targets(targets, counts, ncls, dev)
+        aw = self.anassigner.loss_weights
+        cw = (C.c_float * 5)(aw["total_class"], aw["center"], aw["size"], aw["angle"], self.anassigner.giou_weight)
+        cost = torch.empty((L, B, N, Mmax), dtype=torch.float32, device=dev)
+        n_match = L * B * Mmax * 2
+        n_pack = n_match + L * B
+        tiled = torch.empty(L * B, dtype=torch.int32, device=dev)
+        lib.call("dpft_match_cost_layers_f32", _layer_table(tens, layer_w), L, gt_box.data_ptr(), gt_id.data_ptr(),
+                 counts_t.data_ptr(), C.byref(cw), cost.data_ptr(), tiled.data_ptr(), B, N, Mmax, ncls, stream())
+        hook = self.__dict__.get("_cost_hook")
+        if hook is not None:
+            hook()
+        weights5 = tuple(float(self.loss_weights.get(k, 0.0)) for k in self._TERMS)
+        sel = self.__dict__.get("_sel")
+        if sel is None or sel.device != dev:
+            sel = self.__dict__["_sel"] = torch.tensor([1.0 if k in self.loss_weights else 0.0 for k in self._TERMS],
+                                                       dtype=torch.float32, device=dev)
+        packed_t = torch.empty(n_pack, dtype=torch.int32, device=dev)
+        match_all, counts_all = packed_t[:n_match].view(L, B, Mmax, 2), packed_t[n_match:].view(L, B)
+        match_t, counts_m = match_all[0], counts_all[0]            # layer 0's contiguous slices: what the GIoU term reads
+        losses = torch.empty((L, 5), dtype=torch.float32, device=dev)
+        layer_totals = torch.empty(L, dtype=torch.float32, device=dev)
+        total = torch.empty((), dtype=torch.float32, device=dev)
+        need = int(lib.dpft_set_loss_layers_scratch_floats(L, B, N))
+        st_ = stream()
+        skey = (dev, int(st_.value or 0))
+        scratch = _loss_scratch.get(skey)
+        if scratch is None or scratch.numel() < need:
+            scratch = _loss_scratch[skey] = torch.zeros(max(need, 1024), dtype=torch.float32, device=dev)
+        # the buffers the producers' backward reads, four per supervised output in the decoder's order (center, size, angle,
+        # class): the final output's first, iteration i's at 4 * (1 + i).  Under no_grad nothing is written into them.
+        tg = self.__dict__.get("fused_grad_targets")
+        grads = None
+        if tg is not None and torch.is_grad_enabled() and len(tg) == 4 * (1 + len(aux)):
+            grads = [(tg[4 * g + 3], tg[4 * g], tg[4 * g + 1], tg[4 * g + 2]) for g in groups]      # -> (dcls, dcenter, dsize, dangle)
+            if not all(t.shape == r.shape and t.is_contiguous() and t.dtype == torch.float32
+                       for gl, tl in zip(grads, tens) for t, r in zip(gl, tl)):
+                grads = None
+        table = _layer_table(tens, layer_w, grads)
+        w5 = (C.c_float * 5)(*weights5)
+        tail = (table, L, gt_box.data_ptr(), gt_onehot.data_ptr(), C.cast(w5, C.c_void_p), 0.75, sel.data_ptr(),
+                scratch.data_ptr(), losses.data_ptr(), layer_totals.data_ptr(), total.data_ptr(), B, N, Mmax, ncls, st_)
+        self.__dict__["_bwd_written"] = None
+        self.__dict__["_status_layers"] = (B, tuple(groups))
+        on_dev = self.assign_on_device and os.environ.get("DPFT_LSAP_DEV", "1") != "0"
+        try:
+            if on_dev:
+                self.check_assignment_status(sync=False)
+                rc = lib.dpft_assign_loss_layers_dev_f32(cost.data_ptr(), tiled.data_ptr(), packed_t.data_ptr(),
+                                                         self._status_word(dev).data_ptr(), *tail)
+            else:
+                pin = self.__dict__.get("_pin_i32")
+                if pin is None or pin.numel() < n_pack:
+                    pin = self.__dict__["_pin_i32"] = torch.empty(max(n_pack, 4096), dtype=torch.int32).pin_memory()
+                cnt = np.asarray(counts, dtype=np.int32)
+                host = self._to_host(cost)                                 # the host path's sync
+                rc = lib.dpft_assign_loss_layers_f32(host.ctypes.data, cnt.ctypes.data, pin.numpy()[:n_pack].ctypes.data,
+                                                     packed_t.data_ptr(), *tail)
+        except Exception:
+            scratch.zero_()
+            raise
+        if rc != 0:
+            scratch.zero_()
+            raise ValueError("assignment / loss failed: " + lib.dpft_last_error().decode())
+        if grads is not None:
+            for g in range(1 + len(aux)):          # an iteration left out of the launch hands a zero gradient on
+                if g not in groups:
+                    for t in tg[4 * g:4 * g + 4]:
+                        t.zero_()
+            self.__dict__["_bwd_written"] = tuple(tg)
+        meta = (tuple(layer_w), gt_box, gt_onehot, match_all, counts_all, weights5, 0.75, sel)
+        losses, layer_totals, total = _SetLossLayersFn.apply(meta, (losses, layer_totals, total), *(t for tl in tens for t in tl))
+        tg0 = None if grads is None else tuple(tg[:4])
+        total, giou = self._giou_term(center, size, angle, total, gt_box, match_t, counts_m, tg0)
+        self.__dict__["_last_layers"] = (tens, tuple(groups), tuple(layer_w), match_all, counts_all, len(aux))
+        self.__dict__["_last"] = (cls, center, size, angle, gt_box, gt_onehot, match_t, counts_m, weights5, 0.75, sel, total)
+        batch_losses = self._batch_losses(losses[0], giou)
+        zero = None
+        for i, k in enumerate(aux_keys):
+            if 1 + i in groups:
+                batch_losses[k] = layer_totals[groups.index(1 + i)]
+            else:
+                zero = torch.zeros((), dtype=torch.float32, device=dev) if zero is None else zero
+                batch_losses[k] = zero
+        return total, batch_losses
+
     def _giou_term(self, center, size, angle, total, gt_box, match, counts, grad_targets):
         """(total, None) with the key absent -- no launch, the five-term total as it is.  Otherwise (total + term, term) from the
         GIoU forward launch, which reads the match table and the matched counts where the assignment left them on the device;
@@ -530,21 +714,47 @@ class Loss(nn.modules.loss._Loss):
         """The configured terms in the order of ``loss_weights`` (views, for logging)."""
         return {k: giou if k == self._GIOU else losses5[self._TERMS.index(k)] for k in self.loss_weights}
 
-    def backward_into(self, total: torch.Tensor, dcenter, dsize, dangle, dcls) -> bool:
+    def backward_into(self, total: torch.Tensor, dcenter, dsize, dangle, dcls, *aux_buffers) -> bool:
         """d total / d (center, size, angle, class) of the LAST fused forward, written into the given buffers by the one
-        backward launch (what ``total.backward()`` would hand to the producers of the outputs, without autograd)."""
+        backward launch (what ``total.backward()`` would hand to the producers of the outputs, without autograd).  After a
+        deep-supervision forward ``aux_buffers`` names four more buffers per intermediate iteration, in the same order."""
         import ctypes as C
         from dpft_amd.hip.lib import lib, stream
         last = self.__dict__.pop("_last", None)
         w_giou = self.__dict__.pop("_last_giou", None)
+        layers = self.__dict__.pop("_last_layers", None)
         if last is None or last[-1] is not total:
             return False
         cls, center, size, angle, gt_box, gt_onehot, match, counts, weights5, alpha, sel, _ = last
         written = self.__dict__.pop("_bwd_written", None)
-        if written is not None and all(a is b for a, b in zip(written, (dcenter, dsize, dangle, dcls))):
-            return True      # dpft_assign_loss_f32 launched the gradient kernel into exactly these buffers
+        named = (dcenter, dsize, dangle, dcls) + tuple(aux_buffers)
+        if layers is not None and len(named) != 4 * (1 + layers[5]):
+            raise ValueError(f"backward_into: the last forward supervised {1 + layers[5]} decoder outputs, "
+                             f"{len(named)} gradient buffers were named (four per output expected)")
+        if layers is None and aux_buffers:
+            raise ValueError("backward_into: aux buffers named, but the last forward was not a deep-supervision forward")
+        if written is not None and len(written) == len(named) and all(a is b for a, b in zip(written, named)):
+            return True      # dpft_assign_loss*_f32 launched the gradient kernel into exactly these buffers
         B, N, ncls = cls.shape
         w = (C.c_float * 5)(*weights5)
+        if layers is not None:
+            tens, groups, layer_w, match_all, counts_all, n_aux = layers
+            grads = [(named[4 * g + 3], named[4 * g], named[4 * g + 1], named[4 * g + 2]) for g in groups]
+            for gl, tl in zip(grads, tens):
+                for t, ref in zip(gl, tl):
+                    assert t.shape == ref.shape and t.is_contiguous() and t.dtype == torch.float32
+            lib.call("dpft_set_loss_layers_bwd_f32", _layer_table(tens, layer_w, grads), len(tens), gt_box.data_ptr(),
+                     gt_onehot.data_ptr(), match_all.data_ptr(), counts_all.data_ptr(), C.byref(w), alpha, sel.data_ptr(), None,
+                     B, N, gt_box.shape[1], ncls, stream())
+            for g in range(1 + n_aux):
+                if g not in groups:
+                    for t in named[4 * g:4 * g + 4]:
+                        t.zero_()
+            if w_giou is not None:
+                lib.call("dpft_giou_loss_bwd_f32", center.data_ptr(), size.data_ptr(), angle.data_ptr(), gt_box.data_ptr(),
+                         match.data_ptr(), counts.data_ptr(), w_giou, None, dcenter.data_ptr(), dsize.data_ptr(),
+                         dangle.data_ptr(), 1, B, N, gt_box.shape[1], stream())
+            return True
         for t, ref in ((dcenter, center), (dsize, size), (dangle, angle), (dcls, cls)):
             assert t.shape == ref.shape and t.is_contiguous() and t.dtype == torch.float32
         lib.call("dpft_set_loss_bwd_f32", cls.data_ptr(), center.data_ptr(), size.data_ptr(), angle.data_ptr(),
@@ -561,6 +771,15 @@ class Loss(nn.modules.loss._Loss):
         self.__dict__.pop("_last", None)
         self.__dict__.pop("_last_giou", None)
         self.__dict__["last_has_targets"] = None      # (None = unknown: the eager path)
+        self.__dict__.pop("_last_layers", None)
+        if "aux_outputs" in inputs:
+            aux = inputs["aux_outputs"]
+            inputs = type(inputs)((k, v) for k, v in inputs.items() if k != "aux_outputs")
+            if self.aux_weights is not None:
+                if not self._fused_ok(inputs):
+                    raise ValueError("aux_weights: deep supervision exists on the fused path only (CUDA tensors, fp32 outputs, "
+                                     "reduction 'mean', use_fused); there is no eager or CPU implementation of it")
+                return self.forward_fused_layers(inputs, aux, targets)
         if self._fused_ok(inputs):
             return self.forward_fused(inputs, targets)
         if self._GIOU in self.loss_weights:

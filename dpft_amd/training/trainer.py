@@ -14,6 +14,7 @@ from __future__ import annotations
 import contextlib
 import datetime
 import json
+import math
 import os
 import os.path as osp
 
@@ -87,6 +88,37 @@ def parse_ema(value):
         raise ValueError(f"train.ema: decay must be a number in [0, 1), got {value!r}")
     out["decay"] = float(value)
     return out
+
+
+def parse_aux_loss(value, i_iter: int):
+    """``train.aux_loss`` -> the I - 1 weights of the intermediate decoder iterations (deep supervision): ``true`` (1.0 each),
+    a number (that weight each), or ``{"weights": x | [x_0 .. x_{I-2}]}``.  Anything else is a ValueError."""
+    n = int(i_iter) - 1
+    if n < 1:
+        raise ValueError(f"train.aux_loss: the decoder has i_iter = {i_iter} iteration(s), so there is no intermediate output "
+                         "to supervise (expected i_iter >= 2, or the key left out)")
+
+    def number(x):
+        return not isinstance(x, bool) and isinstance(x, (int, float)) and math.isfinite(x) and x >= 0
+
+    expected = (f"train.aux_loss: expected true, a finite number >= 0, or {{'weights': x | [x_0 .. x_{n - 1}]}} with {n} "
+                f"finite numbers >= 0 (one per intermediate decoder iteration)")
+    if isinstance(value, dict):
+        if set(value) != {"weights"}:
+            raise ValueError(f"{expected}, got {value!r}")
+        value = value["weights"]
+        if isinstance(value, (list, tuple)):
+            if len(value) != n or not all(number(x) for x in value):
+                raise ValueError(f"{expected}, got weights {list(value)!r}")
+            return [float(x) for x in value]
+        if not number(value):
+            raise ValueError(f"{expected}, got weights {value!r}")
+        return [float(value)] * n
+    if value is True:
+        return [1.0] * n
+    if not number(value):
+        raise ValueError(f"{expected}, got {value!r}")
+    return [float(value)] * n
 
 
 def ema_decay_f32(decay) -> float:
@@ -261,6 +293,18 @@ class DataParallelTrainer:
                 self.optimizer.set_ema(self.ema["decay"], self.ema["warmup"])
             else:
                 self._ema_eager = EagerEMA(self.model.parameters(), self.ema["decay"], self.ema["warmup"])
+        # Optional extension (the reference supervises the last decoder iteration only): train.aux_loss = true | w | {"weights":
+        # ...} matches and supervises every intermediate iteration as well (DETR's aux_loss).  The decoder hands the intermediate
+        # head outputs out (IMPFusion.return_aux, read by enable_graphs at capture), the loss takes all of them in the launches of
+        # one output (Loss.forward_fused_layers).  Training only: validation runs the eval decoder, which returns no aux outputs.
+        self.aux_loss = None
+        if "aux_loss" in train:
+            fuser = getattr(self.model, "fuser", None)
+            if not hasattr(fuser, "return_aux") or not hasattr(self.loss_fn, "aux_weights"):
+                raise ValueError("train.aux_loss: needs the IMPFusion decoder and the set-to-set Loss")
+            self.aux_loss = parse_aux_loss(train["aux_loss"], fuser.i_iter)
+            fuser.return_aux = True
+            self.loss_fn.aux_weights = list(self.aux_loss)
         if self.early_adamw:
             self.optimizer.attach_segments([b["params"] for b in self.reducer.buckets])
             self.reducer.on_bucket_final = self.optimizer.step_segment
@@ -313,7 +357,8 @@ class DataParallelTrainer:
             # the buffers the decoder's backward graph reads its output gradients from: the loss call launches the criterion's
             # gradient kernel into them itself (one C call for the whole host window, Loss.forward_fused)
             go = g.static_grad_outputs
-            self.loss_fn.__dict__["fused_grad_targets"] = (go[0], go[1], go[2], go[3])
+            # (with train.aux_loss: four more per intermediate iteration, in the order of the graph's outputs)
+            self.loss_fn.__dict__["fused_grad_targets"] = tuple(go) if self.aux_loss is not None else (go[0], go[1], go[2], go[3])
         elif hasattr(self.loss_fn, "__dict__"):
             self.loss_fn.__dict__["fused_grad_targets"] = None
         loss, losses = self.loss_fn(output, labels)
@@ -358,7 +403,10 @@ class DataParallelTrainer:
                 self.optimizer.gate_required = gate is not None
                 self.optimizer.set_gate(gate)
             if not local:
-                loss = sum(v.sum() for v in output.values()) * 0.0
+                # (every graph output, the intermediate iterations' under "aux_outputs" included: the zero-valued backward of a
+                # rank without targets has to reach all of them)
+                loss = sum(v.sum() for o in [output, *output.get("aux_outputs", ())] for v in o.values()
+                           if isinstance(v, torch.Tensor)) * 0.0
             if not (local and self._backward_without_engine(loss)):
                 loss.backward()
             self.reducer.finish()
@@ -426,8 +474,8 @@ class DataParallelTrainer:
             return False
         done = []
 
-        def write(go):          # static_grad_outputs = (center, size, angle, class)
-            done.append(self.loss_fn.backward_into(loss, go[0], go[1], go[2], go[3]))
+        def write(go):          # static_grad_outputs = (center, size, angle, class), with train.aux_loss x every iteration
+            done.append(self.loss_fn.backward_into(loss, *(go if self.aux_loss is not None else go[:4])))
         if self.loss_fn.__dict__["_last"][-1] is not loss:
             return False
         g.backward_from(write)
@@ -513,7 +561,8 @@ class DataParallelTrainer:
                                    "a rank saw no batches (sampler / drop_last leave it an empty shard)")
             code = int(n[2])
         if code:
-            raise ValueError(self.loss_fn.describe_assignment_status(code) + (" (on at least one rank)" if self.world > 1 else ""))
+            decoding = self.loss_fn.status_decoding() if hasattr(self.loss_fn, "status_decoding") else ()
+            raise ValueError(self.loss_fn.describe_assignment_status(code, *decoding) + (" (on at least one rank)" if self.world > 1 else ""))
         if not scalars:
             return scalars
         keys = sorted(scalars)

@@ -770,6 +770,61 @@ int dpft_set_loss_bwd_f32(const float* cls, const float* center, const float* si
                           int32_t Mmax, int32_t C, dpft_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Deep supervision (train.aux_loss): matcher cost, assignment, criterion and gradient over L supervised outputs ("layers";
+ * layer 0 = the final decoder iteration, layer 1 + i = iteration i) with the launches of one output.  The layers are separate
+ * allocations (a decoder graph's static output / gradient buffers): `layers` is a HOST array of L entries whose pointers
+ * travel by value in the kernel arguments -- no stacking copy, no table upload.  Targets are shared: pseudo-sample
+ * s = l * B + b reads gt_*[b].  Per-query and per-pair arithmetic are the __device__ functions the single-output kernels
+ * call (csrc/misc.hip: match_cost_entry, set_loss_point), so entry [l] of every result has the bits of the single-output
+ * entry on layer l's tensors.  Refused with a message: L < 1 or L > DPFT_LOSS_MAX_LAYERS, a null output, some but not all
+ * gradient pointers of a layer, a negative or non-finite weight (dpft_loss_layers_check, called first by every entry).
+ * ---------------------------------------------------------------------------------------- */
+#define DPFT_LOSS_MAX_LAYERS 8
+typedef struct dpft_loss_layer {
+    const float *cls, *center, *size, *angle; /* (B,N,C) (B,N,3) (B,N,3) (B,N,2) DEVICE, contiguous */
+    float *dcls, *dcenter, *dsize, *dangle;   /* gradient buffers of the same shapes: all four or all NULL */
+    float weight;                             /* of this layer's total in `total` and in its gradient */
+} dpft_loss_layer_t;
+int dpft_loss_layers_check(const dpft_loss_layer_t* layers, int32_t L);
+/* cost (L,B,N,Mmax): entry [l] = dpft_match_cost_f32 on layer l; counts_tiled (L*B) int32 = counts repeated per layer, so
+ * that dpft_lsap_batch_dev_f32 / dpft_lsap_batch_f32 run unchanged on L*B pseudo-samples.  One launch, grid (.., L). */
+int dpft_match_cost_layers_f32(const dpft_loss_layer_t* layers, int32_t L, const float* gt_box, const int32_t* gt_id,
+                               const int32_t* counts, const float* weights5, float* cost, int32_t* counts_tiled, int32_t B,
+                               int32_t N, int32_t Mmax, int32_t C, dpft_stream_t stream);
+/* match (L,B,Mmax,2), counts (L,B) = the assignment of the L*B pseudo-samples.  One launch, grid (blocks of a layer, L);
+ * scratch: dpft_set_loss_layers_scratch_floats(L,B,N) floats, zero when first handed over, left zero.  The block that draws
+ * the last ticket writes losses (L,5): row l = the five weighted batch-mean terms of layer l (block order, WITHOUT the layer
+ * weight: the bits of dpft_set_loss_fwd_total_f32 on layer l), layer_totals (L) = weight_l * sum_k sel[k] * losses[l,k]
+ * (k ascending) and total = their sum in layer order. */
+int64_t dpft_set_loss_layers_scratch_floats(int32_t L, int32_t B, int32_t N);
+int dpft_set_loss_layers_fwd_total_f32(const dpft_loss_layer_t* layers, int32_t L, const float* gt_box, const float* gt_onehot,
+                                       const int32_t* match, const int32_t* counts, const float* weights5, float alpha,
+                                       const float* sel, float* scratch, float* losses, float* layer_totals, float* total,
+                                       int32_t B, int32_t N, int32_t Mmax, int32_t C, dpft_stream_t stream);
+/* d (gout * total) / d (cls, center, size, angle) of every layer that names gradient buffers (at least one must), one launch:
+ * term k of layer l has the factor (weight_l * gout * sel[k]) * weights5[k] / B, i.e. dpft_set_loss_bwd_f32 with
+ * gout5 = (weight_l * gout) * sel.  gout: DEVICE scalar, NULL = 1. */
+int dpft_set_loss_layers_bwd_f32(const dpft_loss_layer_t* layers, int32_t L, const float* gt_box, const float* gt_onehot,
+                                 const int32_t* match, const int32_t* counts, const float* weights5, float alpha,
+                                 const float* sel, const float* gout, int32_t B, int32_t N, int32_t Mmax, int32_t C,
+                                 dpft_stream_t stream);
+/* The layered twins of dpft_assign_loss_dev_f32 / dpft_assign_loss_f32: assignment of the L*B pseudo-samples
+ * (dpft_lsap_batch_dev_f32 on cost (L,B,N,Mmax) with counts_tiled (L*B) DEVICE; respectively dpft_lsap_batch_f32 on the HOST
+ * copy with counts_host (B) + one upload) -> dpft_set_loss_layers_fwd_total_f32 -> dpft_set_loss_layers_bwd_f32 (gout NULL)
+ * when a layer names gradient buffers; three launches from one call.  packed_* : (L*B*Mmax*2 + L*B) int32 = assignments |
+ * matched counts; layer 0's slices of both are contiguous.  Status codes as dpft_lsap_batch_dev_f32 with sample l * B + b. */
+int dpft_assign_loss_layers_dev_f32(const float* cost, const int32_t* counts_tiled, int32_t* packed_dev, int32_t* status,
+                                    const dpft_loss_layer_t* layers, int32_t L, const float* gt_box, const float* gt_onehot,
+                                    const float* weights5, float alpha, const float* sel, float* scratch, float* losses,
+                                    float* layer_totals, float* total, int32_t B, int32_t N, int32_t Mmax, int32_t C,
+                                    dpft_stream_t stream);
+int dpft_assign_loss_layers_f32(const float* cost_host, const int32_t* counts_host, int32_t* packed_host, int32_t* packed_dev,
+                                const dpft_loss_layer_t* layers, int32_t L, const float* gt_box, const float* gt_onehot,
+                                const float* weights5, float alpha, const float* sel, float* scratch, float* losses,
+                                float* layer_totals, float* total, int32_t B, int32_t N, int32_t Mmax, int32_t C,
+                                dpft_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optional sixth criterion term (train.loss_weights["giou"]; the reference's GIoULoss, src/dprt/training/loss.py:111-173, needs
  * pytorch3d and has no backward): the differentiable GIoU3D of the matched pairs,
  *   term = w_giou / B * sum_b 1 / counts[b] * sum_k (1 - G(pred[b, i_k], gt[b, j_k])) / 2,      (i_k, j_k) = match[b, k]
