@@ -43,7 +43,9 @@ constexpr float kRad2Deg = 57.29577951308232f;
 struct RefPoint {
     float u, v;
 };
-// forward of one view's reference point; when GRAD, also the gradient of (u, v) w.r.t. the center
+// forward of one view's reference point; when GRAD, also the gradient of (u, v) w.r.t. the center.  Conventions of the gradient:
+// a coordinate outside [0, 1] passes none, one exactly on 0 or 1 passes it (torch.clip); w == 0 passes the gradient of the undivided
+// coordinates; poles of the spherical coordinates as stated below (tests/head_lattice.py restates the rule in fp64)
 template <bool GRAD>
 __device__ __forceinline__ RefPoint ref_point(float cx, float cy, float cz, int flag, const float* T, const float* Pm,
                                               float Hs, float Ws, float du, float dv, float* dc) {
@@ -76,22 +78,26 @@ __device__ __forceinline__ RefPoint ref_point(float cx, float cy, float cz, int 
         const float ds1 = Pm[1] * du_ + Pm[5] * dv_ + Pm[9] * dw;
         const float ds2 = Pm[2] * du_ + Pm[6] * dv_ + Pm[10] * dw;
         if (flag) {
+            // Convention at the poles: at the origin (r == 0) the view adds nothing; on the vertical axis (rho == 0, r > 0) only
+            // the range term remains -- azimuth and elevation add exactly zero, where autograd of atan2 / asin gives NaN.
             float dtx = 0.f, dty = 0.f, dtz = 0.f;
             if (r > 0.f) {
                 const float ir = 1.f / r;
                 dtx = ds0 * tx * ir; dty = ds0 * ty * ir; dtz = ds0 * tz * ir;
-                const float c = tz * ir;
-                const float ga = ds2 * kRad2Deg / sqrtf(fmaxf(1.f - c * c, 1e-30f));
-                const float ir3 = ir * ir * ir;
-                dtx += ga * (-tz * tx * ir3);
-                dty += ga * (-tz * ty * ir3);
-                dtz += ga * (ir - tz * tz * ir3);
             }
             const float rho2 = tx * tx + ty * ty;
             if (rho2 > 0.f) {
                 const float gp = ds1 * kRad2Deg / rho2;
                 dtx += gp * (-ty);
                 dty += gp * tx;
+                // d elevation / d t = (kRad2Deg / r^2) (-tz tx / rho, -tz ty / rho, rho): no difference of nearly equal terms,
+                // unlike asin'(tz / r) d(tz / r), whose two factors both cancel near the axis (1 - c^2 and 1/r - tz^2/r^3)
+                const float rho = sqrtf(rho2);
+                const float ge = ds2 * kRad2Deg / (r * r);
+                const float gz = ge * tz / rho;
+                dtx -= gz * tx;
+                dty -= gz * ty;
+                dtz += ge * rho;
             }
             dc[0] = T[0] * dtx + T[4] * dty + T[8] * dtz;
             dc[1] = T[1] * dtx + T[5] * dty + T[9] * dtz;

@@ -604,8 +604,10 @@ int dpft_head_train_bwd_f32(const dpft_head_train* h, int32_t B, int32_t Q, int3
  * Reads of `h`: prev_center (B,Q,3), drefs (V,B,Q,2), T / P / p_rows / shape / shape_stride / has_t; writes dcenter_prev
  * (B,Q,3).  y3 must be NULL.  The rule is the one dpft_head_train_bwd_f32 applies to the center it makes, conventions
  * included: a coordinate outside the clip [0,1] passes no gradient; w == 0 passes the gradient of the undivided
- * coordinates; r == 0 and rho^2 == 0 pass none through the norm / elevation and the azimuth; the arcsin slope is
- * clamped at 1e15.  Views are summed in index order.
+ * coordinates; a coordinate exactly on 0 or 1 passes it (as torch.clip does); at r == 0 (the view's origin) the view
+ * adds nothing; at rho == 0 (its vertical axis) only the range term remains, azimuth and elevation add exactly zero.
+ * Elsewhere d elevation / d t = (180 / pi) / r^2 * (-tz tx / rho, -tz ty / rho, rho), which has no difference of nearly
+ * equal terms and keeps its digits up to the axis.  Views are summed in index order.
  * ---------------------------------------------------------------------------------------- */
 int dpft_ref_points_bwd_f32(const dpft_head_train* h, int32_t B, int32_t Q, int32_t V, dpft_stream_t stream);
 

@@ -109,6 +109,67 @@ def test_bn_pass_entries_refuse_what_their_workers_refuse():
     assert lib.dpft_bn_last_form(C.byref(form)) == 0 and form.value == 0          # nothing launched in this process
 
 
+def test_head_train_entries_refuse_what_hd_fill_and_hd_check_proj_refuse():
+    """dpft_head_train_fwd_f32 / _bwd_f32 / dpft_ref_points_bwd_f32 (decoder_train_h.hip): every refusal of hd_fill and
+    hd_check_proj comes back as DPFT_ERR_ARG with a message before anything is launched (the pointers are never read)."""
+    import ctypes as C
+    from dpft_amd.hip.lib import HeadTrain, lib
+    p = [4096 * (i + 1) for i in range(8)]
+    err = lambda: lib.dpft_last_error()
+    entries = (lib.dpft_head_train_fwd_f32, lib.dpft_head_train_bwd_f32, lib.dpft_ref_points_bwd_f32)
+
+    def base():
+        h = HeadTrain()
+        h.prev_center, h.num_classes = p[0], 2
+        return h
+    for fn in entries:
+        assert fn(None, 1, 1, 1, None) == -1 and err()
+        for V in (0, 5):
+            assert fn(C.byref(base()), 1, 1, V, None) == -1 and b"head_train: bad arguments" in err(), (fn, V)
+        for ncls in (0, 17):
+            h = base()
+            h.num_classes = ncls
+            assert fn(C.byref(h), 1, 1, 1, None) == -1 and b"num_classes must be in [1,16]" in err(), (fn, ncls)
+        h = base()
+        h.prev_center = None
+        assert fn(C.byref(h), 1, 1, 1, None) == -1 and b"prev_center is null" in err(), fn
+
+    # reference points wanted (forward: refs; backward: drefs; ref_points_bwd: always) with the projection inputs incomplete
+    def wanting(which):
+        h = base()
+        if which == 0:
+            h.refs = p[1]
+        elif which == 1:
+            h.y3, h.packed, h.red_w, h.drefs = p[1], p[2], p[3], p[1]
+            for g in range(4):
+                for k in range(3):
+                    h.head_w[g][k] = p[4]
+            h.dy3, h.dcenter_prev, h.rows = p[5], p[6], p[7]
+        else:
+            h.drefs, h.dcenter_prev = p[1], p[6]
+        for v in range(2):
+            h.P[v], h.shape[v], h.T[v], h.p_rows[v], h.has_t[v] = p[2], p[3], p[4], 3, 1
+        return h
+    for which, fn in enumerate(entries):
+        for view in (0, 1):
+            msg = b"projection inputs of view %d missing" % view
+            for field, value in (("P", None), ("shape", None), ("p_rows", 2), ("T", None)):
+                h = wanting(which)
+                getattr(h, field)[view] = value
+                assert fn(C.byref(h), 1, 1, 2, None) == -1 and msg in err(), (fn, view, field)
+    h = wanting(2)
+    h.y3 = p[1]
+    assert lib.dpft_ref_points_bwd_f32(C.byref(h), 1, 1, 2, None) == -1 and b"y3 must be null" in err()
+    # the backward without its outputs, the forward with y3 but without its outputs or weights
+    h = wanting(1)
+    h.rows = None
+    assert lib.dpft_head_train_bwd_f32(C.byref(h), 1, 1, 2, None) == -1 and b"head_train_bwd: null output" in err()
+    h = wanting(1)
+    assert lib.dpft_head_train_fwd_f32(C.byref(h), 1, 1, 2, None) == -1 and b"head_train_fwd: null output" in err()
+    h.head_w[3][2] = None
+    assert lib.dpft_head_train_fwd_f32(C.byref(h), 1, 1, 2, None) == -1 and b"head weight 3.2 is null" in err()
+
+
 def test_every_compute_entry_rejects_null_arguments():
     """Error behaviour of the boundary: every compute entry validates its arguments before touching the device and
     reports DPFT_ERR_ARG + a message through dpft_last_error() (no GPU needed; run in a child process because a missing
