@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "../../include/dpft_hip.h"
+#include "host_consts.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -81,12 +82,14 @@ __device__ __forceinline__ void fill_pro_table(float* tab, const float* bnp, con
 // Forward conv (dpft_conv2d_nhwc_fwd_f32) with the train-mode statistics optionally as column sums.
 // `sums` (may be null; needs `stats`): [4][K] words, zero before the launch -- *sums_used tells whether the launch added to them
 // (otherwise `stats` holds the per-tile table as usual).
-// `pro_sums` (may be null): the prologue's BatchNorm comes as column sums; *pro_sums_used tells whether the kernel taken derives
-// its table from them (otherwise NOTHING was launched: the caller finalizes the layer into `pro_bn` and calls again without)
+// `pro_sums` (may be null): the prologue's BatchNorm comes as column sums; only for a conv whose kernel derives its table from
+// them -- ask conv_fwd_pro_from_sums first and finalize the layer into `pro_bn` where it says no (DPFT_ERR_ARG otherwise);
+// *pro_sums_used reports that they were used
 int conv_fwd_sums(const dpft_conv_desc* d, const float* x, const float* w, const float* bias, const float* pro_bn,
                   int32_t pro_relu, float* y, float* stats, void* workspace, dpft_stream_t stream,
                   unsigned long long* sums = nullptr, bool* sums_used = nullptr,
                   const BnSumsRef* pro_sums = nullptr, bool* pro_sums_used = nullptr);
+bool conv_fwd_pro_from_sums(const dpft_conv_desc* d);      // conv.hip: the forward plan of d with a BatchNorm + ReLU prologue
 int conv_dgrad_fused(const dpft_conv_desc* d, const float* dy, const float* w_t, float* dx, int32_t accumulate,
                      void* workspace, dpft_stream_t stream, BnReduceFuse* fuse);
 // bn.hip -- `act16`: the activation / gradient tensors (y, dout, out, dy, res) are bf16 in memory (the pointers keep
@@ -187,11 +190,6 @@ inline int check_launch(const char* what) {
     }
     return DPFT_OK;
 }
-
-inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
-
-constexpr int kNumCU = 256;   // MI355X
-constexpr int kNumXCD = 8;
 
 // XCD-aware bijective remap of a linear workgroup id: consecutive logical ids land on the same
 // XCD (hardware places block b on XCD b % 8), so neighbouring tiles share that XCD's L2.

@@ -1175,7 +1175,6 @@ __global__ void bias_grad_kernel(const float* __restrict__ dy, float* __restrict
 // The same column sums WITHOUT a cleared output and without atomics (round 4): every block leaves its K partial sums in a
 // slab of the conv workspace (agent-scope stores), takes a ticket, and the block that draws the last one adds the partials
 // in block order and writes db -- one launch, a fixed summation order.  kBiasBlocks blocks at most.
-constexpr int kBiasBlocks = 256;
 __global__ __launch_bounds__(256) void bias_grad_slab_kernel(const float* __restrict__ dy, float* __restrict__ db, int64_t M, int K,
                                                               float* __restrict__ slab, int* __restrict__ ticket) {
     __shared__ float red[256];
@@ -1223,12 +1222,6 @@ struct ProfRec {
     int shape[7];        // B,H,W,C,K,k,stride
     int family;          // which pipe the launch ran on (kFam*), written by the dispatch code, not derived from the shape
 };
-// kernel family of the conv launch being dispatched (bench.py prices each against ITS pipe's peak):
-//   0 fp32 MFMA (v_mfma_f32_32x32x2_f32: igemm_pipe / igemm_vec / wgrad_pipe / wgrad_vec), 1 three-term bf16 split, six
-//   v_mfma_f32_32x32x16_bf16 per fp32 product (conv_x3.hip), 2 bf16 operands on the bf16 MFMA (mixed precision),
-//   3 no matrix core: thin-channel / 16-channel / generic vector-ALU kernels
-enum { kFamF32 = 0, kFamX3 = 1, kFamBf16 = 2, kFamVector = 3 };
-static int g_prof_family = kFamVector;
 static bool g_prof_on = false;
 static bool g_serialize = false;                   // dpft_profile_serialize: one stream, no event brackets
 bool profiling_active() { return g_prof_on || g_serialize; }   // resnet_plan: keep everything on one stream while timing
@@ -1238,6 +1231,7 @@ struct ProfScope {
     bool on;
     hipStream_t st;
     ProfRec r;
+    int family = kFamVector;      // of the launch's plan (kFamVector: conv16, thin-channel, nothing launched)
     ProfScope(int kind, const dpft_conv_desc* d, hipStream_t s) : on(g_prof_on), st(s) {
         if (!on) return;
         r.kind = kind;
@@ -1247,11 +1241,10 @@ struct ProfScope {
         (void)hipEventCreate(&r.e0);
         (void)hipEventCreate(&r.e1);
         (void)hipEventRecord(r.e0, st);
-        g_prof_family = kFamVector;      // the early-return paths (conv16, thin-channel) launch no MFMA kernel
     }
     ~ProfScope() {
         if (!on) return;
-        r.family = g_prof_family;
+        r.family = family;
         (void)hipEventRecord(r.e1, st);
         g_prof.push_back(r);
     }
@@ -1261,208 +1254,31 @@ struct ProfScope {
 #include "conv_pipe.h"
 namespace dpft {
 
-// ---------------------------------------------------------------------------------------------
-// host-side tile selection
-// ---------------------------------------------------------------------------------------------
-struct TileChoice {
-    int bm, bn, splits;
-    bool vec;
-    bool x3 = false;      // chosen for the 3 x bf16 split kernels (compute mode 2, multi-tap filters)
-};
-
-// Workspace layout (round 4): [ticket header: kWsHeader bytes][split-K partial slabs].  The header holds one int per output
-// tile of a split-K launch (IgemmArgs::sk_ticket); it must be ZERO when a buffer is first handed to the library
-// (dpft_conv2d_workspace_init) and every launch leaves it zero again.
-constexpr size_t kWsHeader = 16384;
-constexpr int kWsTickets = (int)(kWsHeader / sizeof(int));
+// ---- host side: what a launch will be is decided in conv_plan.h; here the process-wide mode, the arguments and the launches ----
 static inline float* ws_slabs(void* workspace) { return workspace ? reinterpret_cast<float*>((char*)workspace + kWsHeader) : nullptr; }
-// in-kernel split-K fix-up instead of a reduction launch (DPFT_SK_FIXUP=0: the separate reduction kernels, A/B switch)
-static bool sk_fixup_ok(const IgemmArgs& a, int splits, int kind) {      // kind: 1 forward, 2 data gradient, 4 residual data gradient
-    static const int on = getenv("DPFT_SK_FIXUP") == nullptr ? 7 : atoi(getenv("DPFT_SK_FIXUP"));
-    return (on & kind) && splits > 1 && (a.N & 3) == 0 && a.sub_step <= 1 && (int64_t)splits * a.M * a.N * 4 < (1ll << 31);
-}
 
 // 0 = fp32 MFMA (the reference's arithmetic), 1 = bf16 operands / fp32 accumulation in the forward and data-gradient
 // GEMMs of the C % 64 == 0 convs (BASELINE.json configs[4], "bf16 mixed precision"); process-wide, set between launches
-static int initial_compute_mode() {      // DPFT_CONV_COMPUTE=fp32|bf16|bf16x3 presets the mode (tests, sweeps)
-    const char* e = getenv("DPFT_CONV_COMPUTE");
-    if (!e) return 0;
-    return !strcmp(e, "bf16") ? 1 : (!strcmp(e, "bf16x3") ? 2 : 0);
-}
-static int g_conv_bf16 = initial_compute_mode();
+static int g_conv_bf16 = tuning().compute0;
 // fp32 mode: the big multi-tap GEMMs (3x3 / 7x7 filters over C % 64 == 0 channels, >= 2 GFLOP) run as 3 x bf16 split products on
 // the bf16 matrix cores (conv_x3.hip) -- fp32 operands, fp32 results, error against fp64 BELOW the fp32 MFMA's on every
 // shape of the step (tests/test_gpu_conv_table.py).  dpft_conv_set_split(0) / DPFT_CONV_SPLIT=0: fp32 MFMA everywhere.
-static int g_conv_split = getenv("DPFT_CONV_SPLIT") ? atoi(getenv("DPFT_CONV_SPLIT")) != 0 : 1;
-static int g_split_override = -1;      // workspace sizing: both answers
-int conv_mode_key();
-static bool split_on() {
-    if (g_split_override >= 0) return g_split_override != 0;
-    return g_conv_bf16 == 2 || (g_conv_bf16 == 0 && g_conv_split);
-}
-
-// `taps` = kh * kw of the problem (1 = unknown / not asked): in compute mode 2 the filters with more than one tap -- the
-// deep reductions -- take the 3 x bf16 split kernels (conv_x3.hip), whose best tiles differ: their operand stream
-// (6 bytes per element through L2 -> LDS) is what bounds them (tools/x3_abl.sh), so 128 x 128 tiles with a K split
-// that brings the grid to about one workgroup per CU; the 1x1 convs stay on the fp32 MFMA (measured at par there).
-static inline int taps_of(const dpft_conv_desc* d) { return (d->kh * d->kw == 1 && d->stride == 1) ? -1 : d->kh * d->kw; }
-static TileChoice choose_tile(int M, int N, int C, int ksteps, int taps = 1) {
-    TileChoice t;
-    t.vec = (C % BKV) == 0;
-    t.x3 = false;
-    // (only where the GEMM is big enough to be bound by the matrix pipe: the latency-sized problems of the radar encoders
-    // measured 2x SLOWER on the 128-row tiles, profiles/r05_x3_table.txt)
-    // taps = -1: a 1x1 stride-1 conv on fp32 operands; DPFT_X3_1X1_MINK (tuning aid, 0 = off) sends those with a reduction of at
-    // least that many channels to the split kernels too.  Measured in the step (same box, two rounds): off 24.18 / 24.23 ms,
-    // >= 1024 channels 24.66 / 24.71, >= 512 24.68 / 24.90, >= 256 27.5 / 25.8 -- the forward loses as well (1.78 -> 1.81 ms per frame)
-    static const int x1k = getenv("DPFT_X3_1X1_MINK") ? atoi(getenv("DPFT_X3_1X1_MINK")) : 0;
-    const bool deep1x1 = taps == -1 && x1k > 0 && (int64_t)ksteps * BKV >= x1k;
-    if (split_on() && (taps > 1 || deep1x1) && t.vec && getenv("DPFT_FORCE_TILE") == nullptr &&
-        2.0 * M * N * (double)ksteps * BKV >= 2e9) {
-        t.x3 = true;
-        if (N >= 128) {
-            t.bm = 128; t.bn = 128;
-            const int64_t nwg = (int64_t)cdiv(M, 128) * cdiv(N, 128);
-            int sp = (int)std::max<int64_t>(1, std::min<int64_t>(8, kNumCU / nwg));      // at most one workgroup per CU: one round
-            while (sp > 1 && ksteps / sp < 4) --sp;
-            // Few row tiles (batch-1 inference: 15 at layer 3; layer 4 in training): a deep K split of 128 x 128 tiles ends in a
-            // fix-up over 4-8 slabs of 64 KB read by ONE workgroup per tile -- 128 x 64 tiles reach the same workgroup count with
-            // half the split and quarter-size fix-ups: batch-1 forward 3.50 -> 3.10-3.24 ms, training step unchanged
-            // (tools/infer_ab.sh; DPFT_X3_NARROW=0 switches it off, =4 moves the threshold)
-            static const int narrow = getenv("DPFT_X3_NARROW") ? atoi(getenv("DPFT_X3_NARROW")) : 2;
-            if (narrow && sp > narrow) {
-                t.bn = 64;
-                const int64_t nwg64 = (int64_t)cdiv(M, 128) * cdiv(N, 64);
-                sp = (int)std::max<int64_t>(1, std::min<int64_t>(8, kNumCU / nwg64));
-                while (sp > 1 && ksteps / sp < 4) --sp;
-            }
-            t.splits = sp;
-            // (measured, round-5 A/B, docs/history: 128 x 64 tiles without the K split -- which would keep the data gradients' epilogue
-            // operand prefetch -- lose: layer-3 forward 82 vs 70 us per call, data gradient 70 vs 68.5)
-        } else {
-            t.bm = 64; t.bn = 64; t.splits = 1;
-        }
-        return t;
-    }
-    if (const char* f = getenv("DPFT_FORCE_TILE")) {      // tuning aid: "bm,bn,splits"
-        int bm, bn, sp;
-        if (t.vec && sscanf(f, "%d,%d,%d", &bm, &bn, &sp) == 3) {
-            t.bm = bm; t.bn = bn; t.splits = sp < 1 ? 1 : sp;
-            while (t.splits > 1 && ksteps / t.splits < 2) --t.splits;      // every split keeps at least one pipelined K-step
-            return t;
-        }
-    }
-    if (!t.vec) {
-        t.bm = 128;
-        t.bn = (N <= 32) ? 32 : 64;
-        t.splits = 1;
-        return t;
-    }
-    // candidate tiles ordered by per-flop efficiency; pick the one that fills the chip best
-    const int cand[3][2] = {{128, 128}, {128, 64}, {64, 64}};
-    double eff[3] = {1.0, 0.92, 0.80};
-    // Short reductions over many row tiles (the 1x1 convs of camera layers 1-2, K <= 256): the kernel is its epilogue
-    // (statistics / residual / BatchNorm-reduction operands, staged stores), and with 128 x 128 tiles all workgroups of a
-    // wave reach it together; 128 x 64 measured 10-25 % faster there (round-3 tile A/B, docs/history: 176 -> 129 us on the
-    // 128x228 256<-64 data gradient), not on the 57-row-tile grids of layer 3.
-    static const bool shortk_rule = getenv("DPFT_SHORTK_TILE") == nullptr || atoi(getenv("DPFT_SHORTK_TILE")) != 0;      // A/B switch
-    if (shortk_rule && (int64_t)ksteps * BKV <= 256 && (int64_t)cdiv(M, 128) * cdiv(N, 128) >= 768) {
-        eff[0] = 0.88; eff[1] = 1.0; eff[2] = 0.85;
-    }
-    if (const char* e = getenv("DPFT_TILE_EFF")) {      // tuning aid: "e128x128,e128x64,e64x64[,max row tiles it applies to]"
-        double a0, a1, a2; int rows = 1 << 30;
-        if (sscanf(e, "%lf,%lf,%lf,%d", &a0, &a1, &a2, &rows) >= 3 && cdiv(M, 128) <= rows) { eff[0] = a0; eff[1] = a1; eff[2] = a2; }
-    }
-    double best = -1;
-    t.bm = 64; t.bn = 64;
-    for (int i = 0; i < 3; ++i) {
-        const int bm = cand[i][0], bn = cand[i][1];
-        if (bn > 64 && N <= 64) continue;
-        const int64_t nwg = (int64_t)cdiv(M, bm) * cdiv(N, bn);
-        const int slots = kNumCU * 2;  // two resident workgroups per CU
-        const double waves = (double)nwg / slots;
-        const double fill = waves / ceil(waves);
-        // padding waste in N and M
-        const double pad = ((double)M * N) / ((double)cdiv(M, bm) * bm * (double)cdiv(N, bn) * bn);
-        const double score = eff[i] * fill * pad;
-        if (score > best) {
-            best = score;
-            t.bm = bm;
-            t.bn = bn;
-        }
-    }
-    // split-K when even the smallest tile leaves most CUs idle (radar branches, layer4)
-    const int64_t nwg = (int64_t)cdiv(M, t.bm) * cdiv(N, t.bn);
-    t.splits = 1;
-    // DPFT_SPLIT_BELOW (tuning aid): the isolated 232-tile layer-4 1x1 forward runs 52.9 us split in three vs 35.9 us
-    // unsplit (round-3 tile A/B, docs/history), but over the whole step 128 / 192 / 256 are within run-to-run noise (conv time 28.2 /
-    // 27.9 / 28.0 ms): the threshold stays at one workgroup per CU.
-    static const int split_below = getenv("DPFT_SPLIT_BELOW") ? atoi(getenv("DPFT_SPLIT_BELOW")) : kNumCU;
-    // (round 4) 200 ... 255 tiles with a SHALLOW reduction (<= 32 K-steps: the 1x1 convs of camera layer 4, 232 tiles)
-    // stay unsplit: the split's slab round trip + reduction launch cost more than the idle tenth of the chip
-    // (round-3 tile A/B, docs/history: 16x29 2048->512 forward 53.7 -> 36.9 us, 512->2048 data gradient 55.1 -> 40.1 us)
-    const bool shallow_nearly_full = nwg >= 200 && ksteps <= 32;
-    if (nwg < split_below && ksteps >= 8 && !shallow_nearly_full) {
-        int s = (int)((kNumCU * 2 + nwg - 1) / nwg);
-        s = s > 16 ? 16 : s;
-        while (s > 1 && ksteps / s < 4) --s;
-        t.splits = s;
-    }
-    return t;
-}
-
-// act16 = 2 (bf16 activations and bf16 weights): the 256-row tiles of conv_b16w.hip (eight waves, 64 x 128 / 64 x 64 outputs
-// per wave); the tile may carry a K split (in-launch fix-up).  The tile height must not depend on the workspace:
-// dpft_conv2d_stats_tiles answers without one.  Alone, the 256 x 256 tiles win on the wide short-K 1x1 convs (batch 8,
-// 256 -> 1024 forward + statistics 30.9 -> 22.7 us, its data gradient 28.0 -> 19.3, 128 -> 512 forward 46.1 -> 35.8) and lose on
-// N = 256 problems (57 row tiles: a K split's slab round trip costs more than the idle CUs).  INSIDE the training step the data
-// gradients lose -- a 512-thread workgroup that owns a CU's whole LDS cannot share the CU with the weight-gradient stream's
-// workgroups the way three 48 KB workgroups do -- but the FORWARD has no weight-gradient stream beside it: bf16 batch 8, same box,
-// two rounds: off 22.91 / 22.78 ms, forward only 22.60 / 22.60, forward + data gradients 24.14 / 24.21 (profiles/r06_b16w_*.txt).
-// Default: forward only (DPFT_B16W=2); =1 both, =0 off.
-static bool big16_tile(const dpft_conv_desc* d, const IgemmArgs& a, bool dgrad, bool has_ws, TileChoice& t) {
-    static const int on = getenv("DPFT_B16W") ? atoi(getenv("DPFT_B16W")) : 2;      // 0 off | 1 forward + data gradients | 2 forward only (default)
-    if (!on || d->act16 != 2 || (a.C % BKV) != 0 || (a.N % 128) != 0 || getenv("DPFT_FORCE_TILE") != nullptr) return false;
-    if (on == 2 && dgrad) return false;      // 2: forward convs only (no weight-gradient stream beside them)
-    if (dgrad && d->stride > 1) return false;      // (parity classes / the all-tap form keep their kernels)
-    if ((int64_t)a.B * a.H * a.W * a.C >= (1ll << 29) || (int64_t)a.N * a.Ktot >= (1ll << 29)) return false;
-    const int64_t mt = cdiv(a.M, 256);
-    static const int min256 = getenv("DPFT_B16W_MIN256") ? atoi(getenv("DPFT_B16W_MIN256")) : 100;
-    static const int min128 = getenv("DPFT_B16W_MIN128") ? atoi(getenv("DPFT_B16W_MIN128")) : (1 << 30);      // 256 x 128 tiles: measured at par or behind the four-wave kernels (profiles/r06_b16w_*.txt): off
-    const int ksteps = a.Ktot / BKV;
-    if ((a.N % 256) == 0 && mt * (a.N / 256) >= min256) {
-        t.bm = 256; t.bn = 256; t.splits = 1; t.vec = true; t.x3 = false;
-        return true;
-    }
-    const int64_t n128 = mt * (a.N / 128);
-    if (n128 >= min128) {
-        t.bm = 256; t.bn = 128; t.vec = true; t.x3 = false;
-        int sp = 1;
-        static const int max_split = getenv("DPFT_B16W_SPLIT") ? atoi(getenv("DPFT_B16W_SPLIT")) : 4;      // tuning aid
-        if (has_ws && n128 < 200 && max_split > 1) {
-            sp = (int)std::min<int64_t>(max_split, (kNumCU + n128 / 2) / n128);
-            while (sp > 1 && ksteps / sp < 8) --sp;
-        }
-        t.splits = sp < 1 ? 1 : sp;
-        return true;
-    }
-    return false;
-}
+static int g_conv_split = tuning().split0;
+static PlanMode plan_mode() { return PlanMode{g_conv_bf16, g_conv_bf16 == 2 || (g_conv_bf16 == 0 && g_conv_split)}; }
 
 static void fill_igemm(IgemmArgs& a, const dpft_conv_desc* d, bool dgrad) {
-    a.obn = nullptr; a.oadd = nullptr; a.orelu = 0;
     memset(&a, 0, sizeof(a));
+    const GemmDims g = gemm_dims(d, dgrad);
     a.kh = d->kh; a.kw = d->kw; a.stride = d->stride; a.pad = d->pad;
-    if (!dgrad) {
-        a.B = d->B; a.H = d->H; a.W = d->W; a.C = d->C;
-        a.OH = d->OH; a.OW = d->OW; a.N = d->K;
-    } else {
-        a.B = d->B; a.H = d->OH; a.W = d->OW; a.C = d->K;
-        a.OH = d->H; a.OW = d->W; a.N = d->C;
-    }
-    a.M = a.B * a.OH * a.OW;
-    a.Ktot = a.kh * a.kw * a.C;
-    a.ksteps = (a.C % BKV) == 0 ? a.Ktot / BKV : cdiv(a.Ktot, BK);
+    a.B = d->B; a.C = g.C; a.N = g.N; a.M = g.M; a.Ktot = g.Ktot; a.ksteps = g.ksteps;
+    a.H = dgrad ? d->OH : d->H; a.W = dgrad ? d->OW : d->W;
+    a.OH = dgrad ? d->H : d->OH; a.OW = dgrad ? d->W : d->OW;
+    a.x16 = a.y16 = d->act16 != 0;
+}
+// split-K slabs and tickets of a planned launch (the workspace was required by the entry)
+static void set_split(IgemmArgs& a, const IgemmPlan& p, void* workspace) {
+    if (p.splits > 1) a.partial = ws_slabs(workspace);
+    if (p.fixup) a.sk_ticket = reinterpret_cast<int*>(workspace);      // the last split workgroup of a tile runs the whole epilogue
 }
 
 // launch with dynamic LDS; raises the per-kernel dynamic-LDS cap once (tiles above 64 KiB)
@@ -1473,158 +1289,85 @@ static void launch_lds(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t 
     hipLaunchKernelGGL(kernel, grid, block, lds, st, args);
 }
 
-
+// Launches the kernel the plan names, on the tile the plan names; decides nothing.
 template <bool DGRAD>
-static int launch_igemm(IgemmArgs& a, const TileChoice& t, bool pro, hipStream_t st) {
-    if (t.vec) {      // the vector loader keeps a 32-bit tap mask per row and 32-bit buffer offsets
+static int launch_igemm(IgemmArgs& a, const IgemmPlan& p, bool pro, hipStream_t st) {
+    if (p.vec) {      // the vector loader keeps a 32-bit tap mask per row and 32-bit buffer offsets
         DPFT_REQUIRE(a.kh <= 8 && a.kw <= 8, "conv: the C %% 64 == 0 path supports filters up to 8x8 (%dx%d)", a.kh, a.kw);
         DPFT_REQUIRE((int64_t)a.B * a.H * a.W * a.C < (1ll << 29) && (int64_t)a.N * a.Ktot < (1ll << 29),
                      "conv: operand larger than 2 GiB");
     }
     static const int ablate_env = getenv("DPFT_ABLATE") ? atoi(getenv("DPFT_ABLATE")) : 0;
     a.ablate = ablate_env;
-    const bool nonlin = DGRAD && t.vec && a.stride > 1 && a.sub_step <= 1;
-    // fp32, linear taps: the software-pipelined kernel (conv_pipe.h) -- LDS-DMA operands, one barrier per K-step.
-    // DPFT_PIPE=0 keeps igemm_vec_kernel (A/B measurements).
-    static const int pipe_env = getenv("DPFT_PIPE") ? atoi(getenv("DPFT_PIPE")) : 3;      // bit 0: igemm, bit 1: wgrad
-    const bool pipe = t.vec && g_conv_bf16 != 1 && (pipe_env & 1) && !a.x16 && !a.y16 && (!pro || a.pro_relu);
-    // a 64 x 128 tile (DPFT_FORCE_TILE only) exists in the pipelined fp32 kernel alone: every other kernel runs 64 x 64 tiles,
-    // and the grid is counted in those
-    const bool only64 = t.bm == 64 && t.bn == 128 && !pipe;
-    const int bm = nonlin ? 64 : t.bm, bn = (nonlin || only64) ? 64 : t.bn;
-    a.mtiles = cdiv(a.M, bm);
-    a.ntiles = cdiv(a.N, bn);
-    a.splits = t.splits;
+    a.epf = p.epf;
+    a.mtiles = cdiv(a.M, p.bm); a.ntiles = cdiv(a.N, p.bn); a.splits = p.splits;
+    a.ksteps = a.ksteps * BKV / p.pbk;      // (a parity class of a strided data gradient covers a subset of the taps)
     a.ksteps_per_split = cdiv(a.ksteps, a.splits);
-    const int nwg = a.mtiles * a.ntiles * a.splits;
-    DPFT_REQUIRE(!a.sk_ticket || a.mtiles * a.ntiles <= kWsTickets, "conv: %d output tiles exceed the split-K ticket header", a.mtiles * a.ntiles);
-    dim3 grid(nwg), block(256);
-    g_prof_family = !t.vec ? kFamVector : (g_conv_bf16 == 1 ? kFamBf16 : kFamF32);      // (the x3 branches below override)
-    if (nonlin) {
-        g_prof_family = kFamF32;      // (the all-tap form has no bf16-operand variant: fp32 MFMA in every compute mode)
-        if constexpr (DGRAD) {
-            constexpr size_t lds = (size_t)(64 + 64) * LDK * sizeof(float);
-            launch_lds(igemm_vec_kernel<64, 64, 2, 2, true, false, false>, grid, block, lds, st, a);
+    DPFT_REQUIRE(!p.fixup || a.mtiles * a.ntiles <= kWsTickets, "conv: %d output tiles exceed the split-K ticket header", a.mtiles * a.ntiles);
+    const dim3 grid(a.mtiles * a.ntiles * a.splits), block(256), block2(512);
+    // (any other tile runs 64 x 64)
+    const int tile = ((p.bm == 128 && (p.bn == 128 || p.bn == 64)) || (p.bm == 64 && p.bn == 128)) ? p.bm * 1000 + p.bn : 64064;
+#define PIPE_LDS(BM_, BN_, PBK_, ES_) std::max((size_t)2 * (BM_ + BN_) * PBK_ * ES_, (size_t)BM_ * (BN_ + 4) * 4 + (size_t)3 * BN_ * 4)
+#define GO_PIPE(BM_, BN_, PBK_, PRO_, B16_, EPF_)                                                          \
+    launch_lds(igemm_pipe_kernel<BM_, BN_, 2, 2, PBK_, DGRAD, PRO_, B16_, EPF_>, grid, block,              \
+               PIPE_LDS(BM_, BN_, PBK_, (B16_ ? 2 : 4)) + (PRO_ ? (size_t)12 * a.C : 0), st, a)
+// one instantiation of igemm_pipe_kernel, taken where the plan names its tile, K-step and prefetch mode (EpiPrefetch: modes 1, 2 exist
+// for data gradients, 3 for the forward); the operand prologue exists in the plain fp32 forward
+#define PIPE(BM_, BN_, PBK_, B16_, EPF_)                                                                   \
+    if constexpr (EPF_ == 0 || (EPF_ == 3) != DGRAD)                                                       \
+        if (tile == BM_ * 1000 + BN_ && p.pbk == PBK_ && p.epf_kernel == EPF_) {                           \
+            if constexpr (!DGRAD && !B16_ && EPF_ == 0)                                                    \
+                if (pro) { GO_PIPE(BM_, BN_, PBK_, true, false, 0); break; }                               \
+            GO_PIPE(BM_, BN_, PBK_, false, B16_, EPF_);                                                    \
+            break;                                                                                         \
         }
+    switch (p.kernel) {
+    case kAllTap:
+        if constexpr (DGRAD) launch_lds(igemm_vec_kernel<64, 64, 2, 2, true, false, false>, grid, block, (size_t)(64 + 64) * LDK * sizeof(float), st, a);
         return check_launch("conv igemm (strided dgrad, all taps)");
-    }
-    // bf16 activations AND bf16 weights (act16 = 2): both operands go to the matrix cores untouched -- the pipelined kernel
-    // with 2-byte elements, everything by LDS-DMA
-    if (t.vec && a.w16 && a.x16 && !pro && !nonlin) {
-        g_prof_family = kFamBf16;
-        if (t.bm == 256) return launch_igemm_b16w(a, t.bm, t.bn, DGRAD, st);      // conv_b16w.hip: 256-row tiles, eight waves
-        auto go16 = [&](auto kernel, int pbk, size_t lds) {
-            a.ksteps = a.ksteps * BKV / pbk;      // (a parity class of a strided data gradient covers a subset of the taps)
-            a.ksteps_per_split = cdiv(a.ksteps, a.splits);
-            launch_lds(kernel, grid, block, lds, st, a);
-        };
-#define PIPE16_LDS(BM_, BN_, PBK_) std::max((size_t)2 * (BM_ + BN_) * PBK_ * 2, (size_t)BM_ * (BN_ + 4) * 4 + (size_t)3 * BN_ * 4)
-        if constexpr (DGRAD) {      // epilogue operands requested with the first tile (EpiPrefetch; a.epf = its MODE)
-            bool took = true;
-            if (a.epf == 1 && t.bm == 128 && t.bn == 64) go16(igemm_pipe_kernel<128, 64, 2, 2, 64, true, false, true, 1>, 64, PIPE16_LDS(128, 64, 64));
-            else if (a.epf == 2 && t.bm == 128 && t.bn == 64) go16(igemm_pipe_kernel<128, 64, 2, 2, 64, true, false, true, 2>, 64, PIPE16_LDS(128, 64, 64));
-            else if (a.epf == 2 && t.bm == 64 && t.bn == 64 && a.C % 128 == 0) go16(igemm_pipe_kernel<64, 64, 2, 2, 128, true, false, true, 2>, 128, PIPE16_LDS(64, 64, 128));
-            else if (a.epf == 2 && t.bm == 64 && t.bn == 64) go16(igemm_pipe_kernel<64, 64, 2, 2, 64, true, false, true, 2>, 64, PIPE16_LDS(64, 64, 64));
-            else took = false;
-            if (took) return check_launch("conv igemm (pipelined, bf16 operands, epilogue prefetch)");
-        }
-        if (t.bm == 128 && t.bn == 128) go16(igemm_pipe_kernel<128, 128, 2, 2, 64, DGRAD, false, true>, 64, PIPE16_LDS(128, 128, 64));
-        else if (t.bm == 128 && t.bn == 64) go16(igemm_pipe_kernel<128, 64, 2, 2, 64, DGRAD, false, true>, 64, PIPE16_LDS(128, 64, 64));
-        else if (a.C % 128 == 0) go16(igemm_pipe_kernel<64, 64, 2, 2, 128, DGRAD, false, true>, 128, PIPE16_LDS(64, 64, 128));
-        else go16(igemm_pipe_kernel<64, 64, 2, 2, 64, DGRAD, false, true>, 64, PIPE16_LDS(64, 64, 64));
-#undef PIPE16_LDS
-        return check_launch("conv igemm (pipelined, bf16 operands)");
-    }
-    // operands given as three bf16 planes (dpft_conv_desc::a_planes / w_planes): the copy-only split kernel of conv_x3.hip
-    if (t.vec && a.x3 && a.w3 && !pro && !a.x16 && !a.y16 && !a.w16 &&
-        ((t.bm == 128 && (t.bn == 128 || t.bn == 64)) || (t.bm == 64 && t.bn == 64))) {
-        g_prof_family = kFamX3;
-        return launch_igemm_x3(a, t.bm, t.bn, DGRAD, false, st);
-    }
-    a.x3 = a.w3 = nullptr;
-    // fp32 results from the bf16 matrix cores (compute mode 2, conv_x3.hip): three-term split of both operands, six MFMAs
-    static const bool x3_all = getenv("DPFT_X3_ALL") != nullptr && atoi(getenv("DPFT_X3_ALL")) != 0;      // tuning aid: 1x1 convs too
-    if (t.vec && (t.x3 || (g_conv_bf16 == 2 && (x3_all || getenv("DPFT_FORCE_TILE")))) && g_conv_bf16 != 1 && !a.x16 && !a.y16 && !a.w16 && (!pro || a.pro_relu) &&
-        ((t.bm == 128 && (t.bn == 128 || t.bn == 64)) || (t.bm == 64 && t.bn == 64))) {
-        g_prof_family = kFamX3;
-        return launch_igemm_x3(a, t.bm, t.bn, DGRAD, pro, st);
-    }
-    if (pipe) {
-        g_prof_family = kFamF32;
-        static const int shortk_env = getenv("DPFT_SHORTK") ? atoi(getenv("DPFT_SHORTK")) : 0;      // tuning aid
-        const bool short_k = shortk_env > 0 && a.Ktot <= shortk_env;
-        auto go = [&](auto kernel, int pbk, size_t lds) {
-            a.ksteps = a.ksteps * BKV / pbk;
-            a.ksteps_per_split = cdiv(a.ksteps, a.splits);
-            launch_lds(kernel, grid, block, lds, st, a);
-        };
-#define PIPE_LDS(BM_, BN_, PBK_) std::max((size_t)2 * (BM_ + BN_) * PBK_ * 4, (size_t)BM_ * (BN_ + 4) * 4 + (size_t)3 * BN_ * 4)
-#define LAUNCH_PIPE(BM_, BN_, PBK_)                                                                       \
-    do {                                                                                                  \
-        if (pro) go(igemm_pipe_kernel<BM_, BN_, 2, 2, PBK_, DGRAD, !DGRAD>, PBK_, PIPE_LDS(BM_, BN_, PBK_) + (size_t)12 * a.C); \
-        else go(igemm_pipe_kernel<BM_, BN_, 2, 2, PBK_, DGRAD, false>, PBK_, PIPE_LDS(BM_, BN_, PBK_));      \
-    } while (0)
-        if constexpr (DGRAD) {      // epilogue operands requested with the first tile (EpiPrefetch; a.epf = its MODE)
-            bool took = !pro;
-            if (pro) {}
-            else if (a.epf == 1 && t.bm == 128 && t.bn == 64) go(igemm_pipe_kernel<128, 64, 2, 2, 32, true, false, false, 1>, 32, PIPE_LDS(128, 64, 32));
-            else if (a.epf == 2 && t.bm == 128 && t.bn == 64) go(igemm_pipe_kernel<128, 64, 2, 2, 32, true, false, false, 2>, 32, PIPE_LDS(128, 64, 32));
-            else if (a.epf == 2 && t.bm == 64 && t.bn == 64 && !short_k) go(igemm_pipe_kernel<64, 64, 2, 2, 64, true, false, false, 2>, 64, PIPE_LDS(64, 64, 64));
-            else took = false;
-            if (took) return check_launch("conv igemm (pipelined, epilogue prefetch)");
-        }
-        if constexpr (!DGRAD) {      // inference epilogue with a residual: the residual is requested with the first tile (EpiPrefetch mode 3)
-            bool took = !pro && a.epf == 3;
-            if (!took) {}
-            else if (t.bm == 128 && t.bn == 128) go(igemm_pipe_kernel<128, 128, 2, 2, 32, false, false, false, 3>, 32, PIPE_LDS(128, 128, 32));
-            else if (t.bm == 128 && t.bn == 64) go(igemm_pipe_kernel<128, 64, 2, 2, 32, false, false, false, 3>, 32, PIPE_LDS(128, 64, 32));
-            else if (t.bm == 64 && t.bn == 64 && !short_k) go(igemm_pipe_kernel<64, 64, 2, 2, 64, false, false, false, 3>, 64, PIPE_LDS(64, 64, 64));
-            else took = false;
-            if (took) return check_launch("conv igemm (pipelined, inference epilogue, residual prefetch)");
-        }
-        if (t.bm == 128 && t.bn == 128) LAUNCH_PIPE(128, 128, 32);
-        else if (t.bm == 128 && t.bn == 64) LAUNCH_PIPE(128, 64, 32);
-        else if (t.bm == 64 && t.bn == 128) LAUNCH_PIPE(64, 128, 32);
-        else if (short_k) LAUNCH_PIPE(64, 64, 32);      // 32 KB of LDS: more resident workgroups to overlap prologues / epilogues
-        else LAUNCH_PIPE(64, 64, 64);
-#undef LAUNCH_PIPE
-#undef PIPE_LDS
-        return check_launch("conv igemm (pipelined)");
-    }
-    // K-split form (512 threads per tile) where the grid leaves the chip latency-bound: fewer than 3 workgroups per CU and
-    // a reduction deep enough to amortise the hand-over.  Measured (tools/ksplit_ab.sh): -8...-10 % on the data gradients
-    // of the 64 x 64-tile problems (layer-3 3x3: 102 -> 93.5 us), nothing or a loss on the forward kernels (prologue,
-    // statistics epilogue) and on the 128-row tiles (one workgroup per CU either way) -- waves of ONE workgroup march in
-    // step between barriers, so they do not fill each other's stalls the way a second resident workgroup does.  (A two-wave
-    // 64 x 32 tile -- twice the workgroups -- was 15-90 % slower on the same problems: tools/tile6432.sh, removed.)
-    static const int ks_env = getenv("DPFT_KSPLIT") ? atoi(getenv("DPFT_KSPLIT")) : -1;      // tuning aid: 0 / 1 force
-    const bool ks2 = DGRAD && !pro && bm == 64 && bn == 64 &&
-                     (ks_env >= 0 ? ks_env != 0 : (nwg < kNumCU * 3 && a.ksteps_per_split >= 8));
-    const dim3 block2(512);
-#define LAUNCH_VEC(BM_, BN_, WGM_, WGN_)                                                      \
+    case kB16w: return launch_igemm_b16w(a, p.bm, p.bn, DGRAD, st);      // conv_b16w.hip: 256-row tiles, eight waves
+    case kX3Planes: return launch_igemm_x3(a, p.bm, p.bn, DGRAD, false, st);
+    case kX3: return launch_igemm_x3(a, p.bm, p.bn, DGRAD, pro, st);
+    case kPipe16:      // everything by LDS-DMA, 2-byte elements
+        PIPE(128, 64, 64, true, 1) PIPE(128, 64, 64, true, 2) PIPE(64, 64, 128, true, 2) PIPE(64, 64, 64, true, 2)
+        PIPE(128, 128, 64, true, 0) PIPE(128, 64, 64, true, 0) PIPE(64, 64, 128, true, 0) PIPE(64, 64, 64, true, 0)
+        DPFT_REQUIRE(false, "conv igemm: no pipelined bf16 kernel for the planned tile");
+    case kPipe:      // (64 x 64 with 32-wide K-steps: 32 KB of LDS, more resident workgroups to overlap prologues / epilogues)
+        PIPE(128, 64, 32, false, 1) PIPE(128, 64, 32, false, 2) PIPE(64, 64, 64, false, 2)
+        PIPE(128, 128, 32, false, 3) PIPE(128, 64, 32, false, 3) PIPE(64, 64, 64, false, 3)
+        PIPE(128, 128, 32, false, 0) PIPE(128, 64, 32, false, 0) PIPE(64, 128, 32, false, 0) PIPE(64, 64, 32, false, 0) PIPE(64, 64, 64, false, 0)
+        DPFT_REQUIRE(false, "conv igemm: no pipelined kernel for the planned tile");
+    case kVec:
+    case kVecKS2: {
+        const bool ks2 = p.kernel == kVecKS2, b16 = p.family == kFamBf16;
+#define LAUNCH_VEC(BM_, BN_)                                                                  \
     do {                                                                                      \
         constexpr size_t lds = (size_t)(BM_ + BN_) * LDK * sizeof(float);                     \
-        if (g_conv_bf16 == 1 && ks2) {                                                        \
-            if constexpr (DGRAD && BM_ == 64 && BN_ == 64)                                    \
-                launch_lds(igemm_vec_kernel<BM_, BN_, WGM_, WGN_, true, false, true, true, 2>, grid, block2, lds, st, a); \
-        } else if (g_conv_bf16 == 1) {                                                        \
-            if (pro) launch_lds(igemm_vec_kernel<BM_, BN_, WGM_, WGN_, DGRAD, !DGRAD, true, true>, grid, block, lds, st, a); \
-            else launch_lds(igemm_vec_kernel<BM_, BN_, WGM_, WGN_, DGRAD, false, true, true>, grid, block, lds, st, a);      \
-        } else if (ks2) {                                                                     \
-            if constexpr (DGRAD && BM_ == 64 && BN_ == 64)                                    \
-                launch_lds(igemm_vec_kernel<BM_, BN_, WGM_, WGN_, true, false, true, false, 2>, grid, block2, lds, st, a); \
-        } else if (pro) launch_lds(igemm_vec_kernel<BM_, BN_, WGM_, WGN_, DGRAD, !DGRAD>, grid, block, lds, st, a); \
-        else launch_lds(igemm_vec_kernel<BM_, BN_, WGM_, WGN_, DGRAD, false>, grid, block, lds, st, a);      \
+        if (ks2) {                                                                            \
+            if constexpr (DGRAD && BM_ == 64 && BN_ == 64) {                                  \
+                if (b16) launch_lds(igemm_vec_kernel<BM_, BN_, 2, 2, true, false, true, true, 2>, grid, block2, lds, st, a);       \
+                else launch_lds(igemm_vec_kernel<BM_, BN_, 2, 2, true, false, true, false, 2>, grid, block2, lds, st, a);          \
+            }                                                                                 \
+        } else if (b16) {                                                                     \
+            if (pro) launch_lds(igemm_vec_kernel<BM_, BN_, 2, 2, DGRAD, !DGRAD, true, true>, grid, block, lds, st, a); \
+            else launch_lds(igemm_vec_kernel<BM_, BN_, 2, 2, DGRAD, false, true, true>, grid, block, lds, st, a);      \
+        } else if (pro) launch_lds(igemm_vec_kernel<BM_, BN_, 2, 2, DGRAD, !DGRAD>, grid, block, lds, st, a); \
+        else launch_lds(igemm_vec_kernel<BM_, BN_, 2, 2, DGRAD, false>, grid, block, lds, st, a);      \
     } while (0)
-    if (t.vec) {
-        if (t.bm == 128 && t.bn == 128) LAUNCH_VEC(128, 128, 2, 2);
-        else if (t.bm == 128 && t.bn == 64) LAUNCH_VEC(128, 64, 2, 2);
-        else LAUNCH_VEC(64, 64, 2, 2);
-    } else {
-        if (t.bn == 32) hipLaunchKernelGGL((igemm_gen_kernel<32, DGRAD>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((igemm_gen_kernel<64, DGRAD>), grid, block, 0, st, a);
-    }
+        if (tile == 128128) LAUNCH_VEC(128, 128);
+        else if (tile == 128064) LAUNCH_VEC(128, 64);
+        else LAUNCH_VEC(64, 64);
 #undef LAUNCH_VEC
+        break;
+    }
+    default:      // kGeneric
+        if (p.bn == 32) hipLaunchKernelGGL((igemm_gen_kernel<32, DGRAD>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((igemm_gen_kernel<64, DGRAD>), grid, block, 0, st, a);
+        break;
+    }
+#undef PIPE
+#undef GO_PIPE
+#undef PIPE_LDS
     return check_launch("conv igemm");
 }
 
@@ -1632,88 +1375,49 @@ static int launch_igemm(IgemmArgs& a, const TileChoice& t, bool pro, hipStream_t
 #include "conv16_kernels.h"
 namespace dpft {
 
-// thin-channel fast paths (conv16_kernels.h); `handled` tells the caller whether the launch was taken
-// `db` (may be null): also wanted -- the bias gradient sum_p dy[p][k]; *bias_done tells whether the launch carried it
-static int thin_wgrad(const dpft_conv_desc* d, const float* x, const float* dy, float* dw, void* workspace,
-                      hipStream_t st, bool& handled, float* db = nullptr, bool* bias_done = nullptr) {
-    handled = false;
-    if (bias_done) *bias_done = false;
-    if (!workspace) return DPFT_OK;
-    workspace = ws_slabs(workspace);      // the slabs start behind the ticket header
-    if (conv16_matches(d)) {
-        handled = true;
-        static const bool tiled = getenv("DPFT_WGRAD16_TILED") == nullptr || atoi(getenv("DPFT_WGRAD16_TILED")) != 0;      // A/B switch
-        int nb;
-        if (tiled) {
-            nb = conv16_wgrad_tiled_blocks(d);
-            Wgrad16TArgs a{x, dy, (float*)workspace, d->B, d->H, d->W, cdiv(d->W, T16W), cdiv(d->H, T16H),
-                           d->B * cdiv(d->H, T16H) * cdiv(d->W, T16W), db ? 1 : 0};
-            hipLaunchKernelGGL(wgrad16_3x3_tiled_kernel, dim3(nb), dim3(256), 0, st, a);
-            if (db) {
-                int rc = check_launch("conv16 wgrad");
-                if (rc) return rc;
-                hipLaunchKernelGGL(slab_reduce_bias_kernel, dim3(cdiv(2320, 16)), dim3(256), 0, st, (const float*)workspace, dw, db,
-                                   2320, nb, 0, 2304);
-                *bias_done = true;
-                return check_launch("conv16 wgrad + bias reduce");
-            }
-        } else {
-            nb = conv16_wgrad_blocks(d);
-            Wgrad16Args a{x, dy, (float*)workspace, d->B, d->H, d->W, cdiv(d->W, 4), (long)d->B * d->H * cdiv(d->W, 4)};
-            hipLaunchKernelGGL(wgrad16_3x3_kernel, dim3(nb), dim3(256), 0, st, a);
-        }
-        int rc = check_launch("conv16 wgrad");
-        if (rc) return rc;
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(2304, 16)), dim3(256), 0, st, (const float*)workspace, dw, 2304, nb);
-        return check_launch("conv16 wgrad reduce");
+// thin-channel weight gradients (conv16_kernels.h) as planned: p.blocks slabs in the workspace, then the slab reduction
+// `db`: the bias gradient sum_p dy[p][k], carried where p.reduce == kWgReduceSlabBias
+static int thin_wgrad(const dpft_conv_desc* d, const WgradPlan& p, const float* x, const float* dy, float* dw, float* db, void* workspace,
+                      hipStream_t st) {
+    float* slabs = ws_slabs(workspace);      // the slabs start behind the ticket header
+    const bool with_bias = p.reduce == kWgReduceSlabBias;
+    const dim3 grid(p.blocks), block(256);
+    const long M = (long)d->B * d->H * d->W;
+    int n = d->K * d->C, cols = 0;      // floats of dw; bias sums: column `cols` of every row (thin 1x1), or behind the n floats (cols = 0)
+    switch (p.kernel) {
+    case kWgConv16Tiled: {
+        Wgrad16TArgs a{x, dy, slabs, d->B, d->H, d->W, cdiv(d->W, T16W), cdiv(d->H, T16H), d->B * cdiv(d->H, T16H) * cdiv(d->W, T16W), with_bias ? 1 : 0};
+        hipLaunchKernelGGL(wgrad16_3x3_tiled_kernel, grid, block, 0, st, a);
+        n = 2304;
+        break;
     }
-    static const bool stem_tiled = getenv("DPFT_WGRAD_STEM") == nullptr || atoi(getenv("DPFT_WGRAD_STEM")) != 0;      // A/B switch
-    if (stem_tiled && wgrad_stem7_matches(d)) {
-        handled = true;
+    case kWgConv16: {
+        Wgrad16Args a{x, dy, slabs, d->B, d->H, d->W, cdiv(d->W, 4), (long)d->B * d->H * cdiv(d->W, 4)};
+        hipLaunchKernelGGL(wgrad16_3x3_kernel, grid, block, 0, st, a);
+        n = 2304;
+        break;
+    }
+    case kWgStem7: {
         const int tw = cdiv(d->OW, STEM_OW), th = cdiv(d->OH, STEM_OH);
-        const int tiles = d->B * th * tw;
-        const int nb = std::max(1, std::min(kNumCU * 2, tiles));      // (<= 512 slabs: the workspace bound of the pixel-split path)
-        WgradStemArgs a{x, dy, (float*)workspace, d->B, d->H, d->W, d->OH, d->OW, tw, th, tiles};
-        hipLaunchKernelGGL(wgrad_stem7_kernel, dim3(nb), dim3(256), 0, st, a);
-        int rc = check_launch("stem wgrad");
-        if (rc) return rc;
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(64 * 147, 16)), dim3(256), 0, st, (const float*)workspace, dw, 64 * 147, nb);
-        return check_launch("stem wgrad reduce");
+        WgradStemArgs a{x, dy, slabs, d->B, d->H, d->W, d->OH, d->OW, tw, th, d->B * th * tw};
+        hipLaunchKernelGGL(wgrad_stem7_kernel, grid, block, 0, st, a);
+        n = 64 * 147;
+        break;
     }
-    if (d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad == 0) {
-        const long M = (long)d->B * d->H * d->W;
-        const int nb = (int)std::max<long>(1, std::min<long>(kNumCU * 2, M / 1024));
-        const int kc = d->K * d->C;
-#define THIN_1X1(K_, C_)                                                                                     \
-    if (d->K == K_ && d->C == C_) {                                                                          \
-        handled = true;                                                                                      \
-        hipLaunchKernelGGL((wgrad1x1_small_kernel<K_, C_>), dim3(nb), dim3(256), 0, st, x, dy, (float*)workspace, M); \
+    default:      // kWgThin1x1; with the bias gradient as a virtual input channel of ones
+        cols = d->C + 1;
+        if (d->K == 3) hipLaunchKernelGGL((wgrad1x1_small_kernel<3, 6>), grid, block, 0, st, x, dy, slabs, M);
+        else if (d->C == 3 && with_bias) hipLaunchKernelGGL((wgrad1x1_k16_kernel<3, true>), grid, block, 0, st, x, dy, slabs, M);
+        else if (with_bias) hipLaunchKernelGGL((wgrad1x1_k16_kernel<6, true>), grid, block, 0, st, x, dy, slabs, M);
+        else if (d->C == 3) hipLaunchKernelGGL((wgrad1x1_k16_kernel<3>), grid, block, 0, st, x, dy, slabs, M);
+        else hipLaunchKernelGGL((wgrad1x1_k16_kernel<6>), grid, block, 0, st, x, dy, slabs, M);
     }
-        if (d->K == 16 && (d->C == 3 || d->C == 6)) {
-            handled = true;
-            if (db) {      // bias gradient as a virtual input channel of ones
-                if (d->C == 3) hipLaunchKernelGGL((wgrad1x1_k16_kernel<3, true>), dim3(nb), dim3(256), 0, st, x, dy, (float*)workspace, M);
-                else hipLaunchKernelGGL((wgrad1x1_k16_kernel<6, true>), dim3(nb), dim3(256), 0, st, x, dy, (float*)workspace, M);
-                int rc = check_launch("thin 1x1 wgrad");
-                if (rc) return rc;
-                const int cols = d->C + 1;
-                hipLaunchKernelGGL(slab_reduce_bias_kernel, dim3(cdiv(16 * cols, 16)), dim3(256), 0, st, (const float*)workspace, dw, db,
-                                   16 * cols, nb, cols, 0);
-                *bias_done = true;
-                return check_launch("thin 1x1 wgrad + bias reduce");
-            }
-            if (d->C == 3) hipLaunchKernelGGL((wgrad1x1_k16_kernel<3>), dim3(nb), dim3(256), 0, st, x, dy, (float*)workspace, M);
-            else hipLaunchKernelGGL((wgrad1x1_k16_kernel<6>), dim3(nb), dim3(256), 0, st, x, dy, (float*)workspace, M);
-        } else THIN_1X1(3, 6)
-#undef THIN_1X1
-        if (handled) {
-            int rc = check_launch("thin 1x1 wgrad");
-            if (rc) return rc;
-            hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(kc, 16)), dim3(256), 0, st, (const float*)workspace, dw, kc, nb);
-            return check_launch("thin 1x1 wgrad reduce");
-        }
-    }
-    return DPFT_OK;
+    int rc = check_launch("thin wgrad");
+    if (rc) return rc;
+    const int nb = cols ? 16 * cols : kConv16Slab;      // floats per slab with the bias sums
+    if (with_bias) hipLaunchKernelGGL(slab_reduce_bias_kernel, dim3(cdiv(nb, 16)), block, 0, st, (const float*)slabs, dw, db, nb, p.blocks, cols, cols ? 0 : n);
+    else hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(n, 16)), block, 0, st, (const float*)slabs, dw, n, p.blocks);
+    return check_launch("thin wgrad reduce");
 }
 
 static int check_desc(const dpft_conv_desc* d) {
@@ -1737,29 +1441,23 @@ static int check_desc(const dpft_conv_desc* d) {
 
 using namespace dpft;
 
+// Worst case over the slabs of every form of the problem: the contract's BOUNDS, not one plan's slabs (the plans never ask for more)
 extern "C" int64_t dpft_conv2d_workspace_bytes(const dpft_conv_desc* d) {
     if (check_desc(d) != DPFT_OK) return -1;
-    // worst case over fwd / dgrad / wgrad split-K partials
     int64_t best = 0;
-    if (conv16_matches(d)) best = std::max<int64_t>(best, (int64_t)conv16_wgrad_blocks(d) * 2320 * 4);      // (+ bias column sums)
-    if (d->kh == 1 && d->kw == 1 && d->K <= 16 && d->C <= 8) best = std::max<int64_t>(best, (int64_t)kNumCU * 2 * d->K * (d->C + 1) * 4);
-    for (int mode : {0, 1}) {      // with or without the split kernels, whichever the launches will run with (they pick their own splits)
-        g_split_override = mode;
-        for (int dg = 0; dg < 2; ++dg) {
-            IgemmArgs a; fill_igemm(a, d, dg != 0);
-            TileChoice t = choose_tile(a.M, a.N, a.C, a.ksteps, d->act16 ? 1 : taps_of(d));
+    if (conv16_matches(d)) best = std::max<int64_t>(best, (int64_t)conv16_wgrad_blocks(d) * kConv16Slab * 4);      // (both forms, + bias column sums)
+    if (d->kh == 1 && d->kw == 1 && d->K <= 16 && d->C <= 8) best = std::max<int64_t>(best, (int64_t)kNumCU * 2 * d->K * (d->C + 1) * 4);      // thin 1x1: blocks <= 2 per CU
+    const ForceTile force;
+    for (bool split_on : {false, true})      // with or without the split kernels, whichever the launches will run with
+        for (bool dgrad : {false, true}) {
+            const GemmDims g = gemm_dims(d, dgrad);
+            TileChoice t = choose_tile(g.M, g.N, g.C, g.ksteps, d->act16 ? 1 : taps_of(d), PlanMode{g_conv_bf16, split_on}, force);
             if (d->act16) t.splits = 1;
-            (void)big16_tile(d, a, dg != 0, true, t);
-            if (t.splits > 1) best = std::max<int64_t>(best, (int64_t)t.splits * a.M * a.N * 4);
+            (void)big16_tile(d, g, dgrad, true, force, t);
+            if (t.splits > 1) best = std::max<int64_t>(best, (int64_t)t.splits * g.M * g.N * 4);
         }
-    }
-    g_split_override = -1;
-    // wgrad: pixel-split partial slabs, at most min(512 splits, 64 MiB)
-    {
-        const int64_t wbytes = (int64_t)d->K * d->kh * d->kw * d->C * 4;
-        const int64_t ms = std::max<int64_t>(1, std::min<int64_t>(512, (64ll << 20) / wbytes));
-        best = std::max<int64_t>(best, ms * wbytes);
-    }
+    const int64_t wbytes = (int64_t)d->K * d->kh * d->kw * d->C * 4;      // wgrad: pixel-split partial slabs
+    best = std::max<int64_t>(best, wgrad_max_splits(wbytes) * wbytes);
     best = std::max<int64_t>(best, (int64_t)kBiasBlocks * std::min(d->K, 256) * 4);      // bias_grad_slab_kernel's partial sums
     return best + (int64_t)kWsHeader;
 }
@@ -1792,25 +1490,49 @@ extern "C" int32_t dpft_conv_get_split() { return dpft::g_conv_split; }
 
 int dpft::conv_mode_key() { return dpft::g_conv_bf16 * 2 + (dpft::g_conv_split ? 1 : 0); }
 
-// The forward conv goes to the streaming 1x1 kernel (conv_stream.hip): the statistics tiling and every forward entry ask this
-static bool takes_stream1x1(const dpft_conv_desc* d, int* tile_rows = nullptr) {
-    return g_conv_bf16 != 1 && stream1x1_match(d, tile_rows);
-}
-
+// The statistics tiling = the tile rows of the forward plan with statistics wanted.  The query does not know the prologue: a
+// multi-tap conv of >= 2 GFLOP in a split-on mode with a prologue WITHOUT ReLU is planned with `taps = 1` by conv_fwd_sums and
+// may get another tile height than the one reported here.  No caller in the repository passes that prologue with statistics.
 extern "C" int32_t dpft_conv2d_stats_tiles(const dpft_conv_desc* d, int32_t* tile_rows) {
     if (check_desc(d) != DPFT_OK) return -1;
-    IgemmArgs a; fill_igemm(a, d, false);
-    {
-        int tr = 0;
-        if (takes_stream1x1(d, &tr)) {      // tile = the rows of one workgroup
-            if (tile_rows) *tile_rows = tr;
-            return cdiv(a.M, tr);
+    IgemmIn in;
+    in.stats = true;
+    const IgemmPlan p = plan_igemm(d, kFwd, in, plan_mode());
+    if (tile_rows) *tile_rows = p.bm;
+    return cdiv((int64_t)d->B * d->OH * d->OW, p.bm);
+}
+
+bool dpft::conv_fwd_pro_from_sums(const dpft_conv_desc* d) {
+    IgemmIn in;
+    in.ws = in.pro = in.pro_relu = in.stats = in.sums = true;
+    return plan_igemm(d, kFwd, in, plan_mode()).pro_from_sums;
+}
+
+// family of the last launch a strided data gradient makes as parity classes (what its profile record holds)
+static int classes_family(const dpft_conv_desc* d, const IgemmIn& in, const PlanMode& mode) {
+    int family = kFamVector;
+    for (int ph = 0; ph < d->stride; ++ph)
+        for (int pw = 0; pw < d->stride; ++pw) {
+            DgradClass c;
+            if (!dgrad_class(d, ph, pw, c)) continue;
+            IgemmIn q = in;
+            q.M = c.M; q.ksteps = c.ksteps;
+            family = plan_igemm(d, kDgradClass, q, mode).family;
         }
+    return family;
+}
+
+extern "C" int32_t dpft_conv2d_planned_family(const dpft_conv_desc* d, int32_t kind, int32_t has_workspace) {
+    if (check_desc(d) != DPFT_OK || kind < 0 || kind > 2) return -1;
+    if (kind == 2) {
+        WgradIn in;
+        in.ws = has_workspace != 0;
+        return plan_wgrad(d, in, plan_mode()).family;
     }
-    TileChoice t = choose_tile(a.M, a.N, a.C, a.ksteps, d->act16 ? 1 : taps_of(d));      // (as conv_fwd_sums asks)
-    (void)big16_tile(d, a, false, false, t);
-    if (tile_rows) *tile_rows = t.bm;
-    return cdiv(a.M, t.bm);
+    IgemmIn in;
+    in.ws = has_workspace != 0;
+    const IgemmPlan p = plan_igemm(d, kind == 0 ? kFwd : kDgrad, in, plan_mode());
+    return p.kernel == kClasses ? classes_family(d, in, plan_mode()) : p.family;
 }
 
 extern "C" int dpft_conv2d_nhwc_fwd_f32(const dpft_conv_desc* d, const float* x, const float* w,
@@ -1830,84 +1552,52 @@ int dpft::conv_fwd_sums(const dpft_conv_desc* d, const float* x, const float* w,
     int rc = check_desc(d);
     if (rc) return rc;
     DPFT_REQUIRE(x && w && y, "conv fwd: null tensor");
-    {
-        static const char* skip = getenv("DPFT_SKIP");      // timing experiments (see dpft_conv2d_nhwc_wgrad_f32)
-        if (skip && ((strstr(skip, "fwd3x3") && d->kh == 3) || (strstr(skip, "fwd1x1") && d->kh == 1)) && (int64_t)d->B * d->OH * d->OW >= 4096) return DPFT_OK;
-    }
+    if (skip_conv("fwd3x3", "fwd1x1", d->kh, (int64_t)d->B * d->OH * d->OW)) return DPFT_OK;
+    const bool pro = pro_bn != nullptr;
+    IgemmIn in;
+    in.ws = workspace != nullptr; in.bias = bias != nullptr; in.pro = pro; in.pro_relu = pro_relu != 0;
+    in.stats = stats != nullptr; in.sums = sums != nullptr; in.planes = d->a_planes && d->w_planes;
+    const IgemmPlan p = plan_igemm(d, kFwd, in, plan_mode());
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof(0, d, st);
-    if (conv16_matches(d) && !pro_bn && !stats) return conv16_forward(d, x, w, bias, y, st);
-    static const bool thin_fwd = getenv("DPFT_THIN_FWD") == nullptr || atoi(getenv("DPFT_THIN_FWD")) != 0;      // A/B switch
-    if (thin_fwd && conv1x1_to16_matches(d) && !pro_bn && !stats) return conv1x1_to16_forward(d, x, w, bias, y, st);
-    if (takes_stream1x1(d)) {
-        // short reduction, wide output, large map: the streaming kernel (conv_stream.hip), which has no bias and only the
-        // BatchNorm + ReLU prologue.  Statistics must come in its tiling (dpft_conv2d_stats_tiles): no other kernel may take them.
-        const bool fits = !bias && (!pro_bn || pro_relu);
-        DPFT_REQUIRE(fits || !stats, "conv fwd: statistics of a streaming 1x1 conv (%d -> %d) take no bias and only the BatchNorm + ReLU prologue", d->C, d->K);
-        if (fits) {
-            g_prof_family = kFamF32;
-            unsigned long long* bns = sums && (int64_t)d->B * d->OH * d->OW < (1 << 22) ? sums : nullptr;
-            if (bns) *sums_used = true;
-            if (pro_sums) *pro_sums_used = true;
-            return launch_stream1x1(d, x, w, pro_bn, y, stats, nullptr, nullptr, 0, st, bns, pro_sums);
-        }
-    }
+    prof.family = p.family;
+    // statistics must come in the tiling dpft_conv2d_stats_tiles reports: no other kernel may take those of a streaming 1x1 shape
+    DPFT_REQUIRE(!(p.stream_unfit && stats), "conv fwd: statistics of a streaming 1x1 conv (%d -> %d) take no bias and only the BatchNorm + ReLU prologue", d->C, d->K);
+    DPFT_REQUIRE(!pro_sums || p.pro_from_sums, "conv fwd: the kernel of this conv builds no prologue from column sums (ask conv_fwd_pro_from_sums first)");
+    if (p.stat_sums) *sums_used = true;      // column sums instead of the per-tile table; finalized by nobody here
+    if (pro_sums) *pro_sums_used = true;
+    if (p.kernel == kConv16) return conv16_forward(d, x, w, bias, y, st);
+    if (p.kernel == kThin) return conv1x1_to16_forward(d, x, w, bias, y, st);
+    if (p.kernel == kStream1x1) return launch_stream1x1(d, x, w, pro_bn, y, stats, nullptr, nullptr, 0, st, p.stat_sums ? sums : nullptr, pro_sums);
+    DPFT_REQUIRE(!(d->act16 == 2 && (bias || pro_bn)), "conv fwd: act16 = 2 (bf16 weights) takes no bias and no operand prologue");
+    DPFT_REQUIRE(!(pro && !p.vec), "conv fwd: fused prologue needs C %% 64 == 0 (C=%d)", d->C);
+    DPFT_REQUIRE(p.splits == 1 || workspace, "conv fwd: split-K selected but no workspace given");
     IgemmArgs a; fill_igemm(a, d, false);
-    a.x = x; a.w = w; a.y = y; a.bias = bias; a.stats = stats;
+    a.x = x; a.w = w; a.y = y; a.bias = bias;
     a.pro = pro_bn; a.pro_relu = pro_relu;
-    a.x16 = a.y16 = d->act16 != 0;
     a.w16 = d->act16 == 2;
-    if (d->a_planes && d->w_planes && !pro_bn && !d->act16) { a.x3 = d->a_planes; a.w3 = d->w_planes; }
-    DPFT_REQUIRE(!(a.w16 && (bias || pro_bn)), "conv fwd: act16 = 2 (bf16 weights) takes no bias and no operand prologue");
-    const bool pro = pro_bn != nullptr;
-    TileChoice t = choose_tile(a.M, a.N, a.C, a.ksteps, (d->act16 || (pro && !pro_relu)) ? 1 : taps_of(d));
-    const bool big16 = !pro && !bias && big16_tile(d, a, false, workspace != nullptr, t);
-    if (d->act16 && !big16) t.splits = 1;      // the split-K reduction kernels write fp32 tensors (big16: in-launch fix-up only)
-    if (big16 && t.splits > 1 && !sk_fixup_ok(a, t.splits, 1)) t.splits = 1;
-    DPFT_REQUIRE(!(pro && !t.vec), "conv fwd: fused prologue needs C %% 64 == 0 (C=%d)", d->C);
-    if (pro_sums) {
-        // the kernels that build their prologue table from the sums: the split kernels and the pipelined fp32 kernel (launch_igemm)
-        static const int pipe_env = getenv("DPFT_PIPE") ? atoi(getenv("DPFT_PIPE")) : 3;
-        if (!(t.vec && g_conv_bf16 != 1 && !d->act16 && pro_relu && (t.x3 || (pipe_env & 1)) && (int64_t)12 * d->C <= 16384)) return DPFT_OK;
-        a.pro_s = *pro_sums;
-        *pro_sums_used = true;
+    if (p.kernel == kX3Planes) { a.x3 = d->a_planes; a.w3 = d->w_planes; }
+    if (pro_sums) a.pro_s = *pro_sums;
+    set_split(a, p, workspace);
+    if (p.stat_sums) a.bns = sums;
+    else if (p.splits == 1 || p.fixup) a.stats = stats;      // (a reduction launch produces them otherwise)
+    rc = launch_igemm<false>(a, p, pro, st);
+    if (rc || p.reduce == kReduceNone) return rc;
+    const int64_t MN = (int64_t)a.M * a.N;
+    if (p.reduce == kReduceStats) {      // reduce + per-tile (mean, M2) in one launch
+        hipLaunchKernelGGL(splitk_reduce_stats_kernel, dim3(cdiv(a.M, p.bm), a.N / 64), dim3(256), 0, st, a.partial, y,
+                           stats, (int64_t)a.M, a.N, p.splits, p.bm);
+        return check_launch("conv fwd split-K reduce + stats");
     }
-    bool fixup = false;
-    if (t.splits > 1) {
-        DPFT_REQUIRE(workspace, "conv fwd: split-K selected but no workspace given");
-        a.partial = ws_slabs(workspace);
-        fixup = sk_fixup_ok(a, t.splits, 1);
-        if (fixup) a.sk_ticket = reinterpret_cast<int*>(workspace);      // the last split workgroup of a tile runs the whole epilogue
-        else a.stats = nullptr;
-    }
-    // (the accumulators' low words hold 65 536 addends: tiles of >= 64 rows)
-    if (sums && !bias && t.vec && (a.N & 3) == 0 && (t.splits == 1 || fixup) && a.M < (1 << 22)) {
-        a.bns = sums;      // column sums instead of the per-tile table; finalized by nobody here
-        a.stats = nullptr;
-        *sums_used = true;
-    }
-    rc = launch_igemm<false>(a, t, pro, st);
-    if (rc) return rc;
-    if (t.splits > 1 && !fixup) {
-        const int64_t MN = (int64_t)a.M * a.N;
-        if (stats && !bias && (a.N % 64) == 0 && t.bm <= 128) {      // reduce + per-tile (mean, M2) in one launch
-            hipLaunchKernelGGL(splitk_reduce_stats_kernel, dim3(cdiv(a.M, t.bm), a.N / 64), dim3(256), 0, st, a.partial, y,
-                               stats, (int64_t)a.M, a.N, t.splits, t.bm);
-            return check_launch("conv fwd split-K reduce + stats");
-        }
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv(MN, 1024)), dim3(256), 0, st, a.partial, bias, y, MN, a.N, t.splits, 0);
-        rc = check_launch("conv fwd split-K reduce");
-        if (rc) return rc;
-        if (stats) {  // stats from the reduced output (tile_rows = t.bm rows per tile)
-            rc = dpft_bn_stats_f32(y, stats, a.M, a.N, t.bm, stream);
-        }
-    }
-    return rc;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv(MN, 1024)), dim3(256), 0, st, a.partial, bias, y, MN, a.N, p.splits, 0);
+    rc = check_launch("conv fwd split-K reduce");
+    if (rc || !stats) return rc;
+    return dpft_bn_stats_f32(y, stats, a.M, a.N, p.bm, stream);      // stats from the reduced output (p.bm rows per tile)
 }
 
 // Inference form of conv + BatchNorm (+ residual) (+ ReLU): y = [relu](bn(conv(x, w)) [+ residual]) with the BN block of the
-// OUTPUT channels.  One launch when the problem takes the vector path without split-K (the epilogue does it); otherwise
-// the plain convolution followed by the elementwise pass -- same arithmetic, same result.
+// OUTPUT channels.  One launch when the problem takes the vector path without split-K (the epilogue does it) or with the
+// in-launch fix-up; otherwise the plain convolution followed by the elementwise pass -- same arithmetic, same result.
 extern "C" int dpft_conv2d_nhwc_fwd_bnact_f32(const dpft_conv_desc* d, const float* x, const float* w, const float* out_bn,
                                               int32_t relu, const float* residual, float* y, void* workspace,
                                               dpft_stream_t stream) {
@@ -1918,40 +1608,23 @@ extern "C" int dpft_conv2d_nhwc_fwd_bnact_f32(const dpft_conv_desc* d, const flo
     // convolution is launched, not by the pass behind it)
     DPFT_REQUIRE(d->K % 4 == 0, "conv fwd_bnact: K %% 4 == 0 needed (K=%d)", d->K);
     hipStream_t st = (hipStream_t)stream;
-    if (takes_stream1x1(d)) {
-        ProfScope prof(0, d, st);
-        g_prof_family = kFamF32;
-        return launch_stream1x1(d, x, w, nullptr, y, nullptr, out_bn, residual, relu, st);
-    }
-    IgemmArgs a; fill_igemm(a, d, false);
-    TileChoice t = choose_tile(a.M, a.N, a.C, a.ksteps, d->act16 ? 1 : taps_of(d));
-    if (d->act16) t.splits = 1;
-    const int64_t M = (int64_t)d->B * d->OH * d->OW;
-    static const bool fix_all = getenv("DPFT_BNACT_FIXUP") == nullptr || atoi(getenv("DPFT_BNACT_FIXUP")) != 0;      // A/B switch
-    if ((t.x3 || (fix_all && t.vec && !conv16_matches(d))) && t.splits > 1 && workspace && sk_fixup_ok(a, t.splits, 1)) {
-        // a K split (the latency-sized problems: batch-1 inference, the radar encoders' maps; the split kernels): the last
-        // workgroup of a tile runs the whole inference epilogue (in-launch fix-up) -- no reduction launch, no elementwise pass
-        ProfScope prof(0, d, st);
-        a.x = x; a.w = w; a.y = y;
-        a.partial = ws_slabs(workspace);
-        a.sk_ticket = reinterpret_cast<int*>(workspace);
-        a.obn = out_bn; a.oadd = residual; a.orelu = relu;
-        return launch_igemm<false>(a, t, false, st);
-    }
-    if (!t.vec || t.splits > 1 || conv16_matches(d)) {
+    IgemmIn in;
+    in.ws = workspace != nullptr; in.residual = residual != nullptr; in.planes = d->a_planes && d->w_planes;
+    const IgemmPlan p = plan_igemm(d, kFwdBnact, in, plan_mode());
+    if (p.kernel == kTwoPass) {
         rc = dpft_conv2d_nhwc_fwd_f32(d, x, w, nullptr, nullptr, 0, y, nullptr, workspace, stream);
         if (rc) return rc;
-        return bn_act_any(y, out_bn, residual, nullptr, relu, y, nullptr, M, d->K, d->act16 != 0, stream);
+        return bn_act_any(y, out_bn, residual, nullptr, relu, y, nullptr, (int64_t)d->B * d->OH * d->OW, d->K, d->act16 != 0, stream);
     }
     ProfScope prof(0, d, st);
-    a.x = x; a.w = w; a.y = y; a.bias = nullptr; a.stats = nullptr; a.pro = nullptr; a.pro_relu = 0;
-    a.x16 = a.y16 = d->act16 != 0;
-    if (d->a_planes && d->w_planes && !d->act16) { a.x3 = d->a_planes; a.w3 = d->w_planes; }
+    prof.family = p.family;
+    if (p.kernel == kStream1x1) return launch_stream1x1(d, x, w, nullptr, y, nullptr, out_bn, residual, relu, st);
+    IgemmArgs a; fill_igemm(a, d, false);
+    a.x = x; a.w = w; a.y = y;
+    if (p.kernel == kX3Planes) { a.x3 = d->a_planes; a.w3 = d->w_planes; }
+    set_split(a, p, workspace);
     a.obn = out_bn; a.oadd = residual; a.orelu = relu;
-    // unsplit fp32 launch with a residual: the residual is read during the main loop instead of after it (DPFT_EPF bit 2)
-    static const int epf_on = getenv("DPFT_EPF") == nullptr ? 7 : atoi(getenv("DPFT_EPF"));
-    if ((epf_on & 4) && residual && !d->act16 && !a.x3 && !t.x3 && (int64_t)a.M * a.N < (1ll << 29) && d->stride == 1 && g_conv_bf16 != 1) a.epf = 3;
-    return launch_igemm<false>(a, t, false, st);
+    return launch_igemm<false>(a, p, false, st);
 }
 
 // One level of the FPN neck's forward as two launches (include/dpft_hip.h): the top-down add rides in the lateral's epilogue on
@@ -1962,10 +1635,8 @@ extern "C" int dpft_fpn_lateral_f32(const dpft_conv_desc* d, const float* x, con
     if (rc) return rc;
     DPFT_REQUIRE(x && w && lat && d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad == 0, "fpn_lateral: a 1x1 conv (stride 1) with its tensors");
     DPFT_REQUIRE(!top || (TH >= 1 && TW >= 1 && TH <= d->H && TW <= d->W && d->K % 4 == 0), "fpn_lateral: bad top level (%d x %d)", TH, TW);
-    static const bool fuse = getenv("DPFT_FPN_FUSE") == nullptr || atoi(getenv("DPFT_FPN_FUSE")) != 0;      // A/B switch
-    if (top && fuse && conv1x1_to16_top_matches(d)) {
+    if (top && tuning().fpn_fuse && conv1x1_to16_top_matches(d)) {
         ProfScope prof(0, d, (hipStream_t)stream);
-        g_prof_family = kFamVector;
         return conv1x1_to16_top_forward(d, x, w, bias, top, TH, TW, lat, (hipStream_t)stream);
     }
     rc = dpft_conv2d_nhwc_fwd_f32(d, x, w, bias, nullptr, 0, lat, nullptr, workspace, stream);
@@ -1979,10 +1650,8 @@ extern "C" int dpft_fpn_output_f32(const dpft_conv_desc* d, const float* lat, co
     if (rc) return rc;
     DPFT_REQUIRE(lat && w && out && (pos_x == nullptr) == (pos_y == nullptr), "fpn_output: null tensor / one embedding table without the other");
     DPFT_REQUIRE(d->H == d->OH && d->W == d->OW, "fpn_output: a same-size conv");
-    static const bool fuse = getenv("DPFT_FPN_FUSE") == nullptr || atoi(getenv("DPFT_FPN_FUSE")) != 0;
-    if (pos_x && fuse && conv16_matches(d) && !d->act16) {
+    if (pos_x && tuning().fpn_fuse && conv16_matches(d) && !d->act16) {
         ProfScope prof(0, d, (hipStream_t)stream);
-        g_prof_family = kFamVector;
         return conv16_forward(d, lat, w, bias, out, (hipStream_t)stream, pos_x, pos_y);
     }
     rc = dpft_conv2d_nhwc_fwd_f32(d, lat, w, bias, nullptr, 0, out, nullptr, workspace, stream);
@@ -1996,29 +1665,45 @@ extern "C" int dpft_conv2d_nhwc_dgrad_f32(const dpft_conv_desc* d, const float* 
     return dpft::conv_dgrad_fused(d, dy, w_t, dx, accumulate, workspace, stream, nullptr);
 }
 
-static void set_bnr(IgemmArgs& a, const dpft::BnReduceFuse* f) {
+// the arguments both data-gradient entries share; the reduction `f` rides in the epilogue where the plan carries it
+static void fill_dgrad(IgemmArgs& a, const dpft_conv_desc* d, const IgemmPlan& p, const float* dy, const float* w_t, float* dx, void* workspace,
+                       dpft::BnReduceFuse* f) {
+    fill_igemm(a, d, true);
+    a.x = dy; a.w = w_t; a.y = dx;
+    a.w16 = d->act16 == 2;
+    if ((p.kernel == kX3Planes || p.kernel == kAllTap) && d->a_planes && d->w_planes && !d->act16) { a.x3 = d->a_planes; a.w3 = d->w_planes; }      // (kAllTap does not read them)
+    set_split(a, p, workspace);
+    if (!p.bnr) return;
     a.bnr_y = f->y; a.bnr_bnp = f->bnp; a.bnr_mask8 = f->mask8; a.bnr_self_mask = f->self_mask; a.bnr_sums = f->sums;
+    f->applied = true;
 }
 
 // Data gradient with an optional fused BatchNorm-backward reduction (BnReduceFuse, common.h): `fuse->applied` tells the
 // caller whether the launch(es) carried it -- split-K and thin-channel paths do not.
-int dpft::conv_dgrad_fused(const dpft_conv_desc* d, const float* dy, const float* w_t, float* dx, int32_t accumulate,
-                           void* workspace, dpft_stream_t stream, BnReduceFuse* fuse) {
+// With `res_src`: dx = dgrad(dy) + (res_mask > 0 ? res_src : 0), the stride-1 data gradient with the identity-branch ReLU
+// backward folded into the epilogue (conv_dgrad_residual, used by the ResNet launch plan).
+static int dgrad_any(const dpft_conv_desc* d, const float* dy, const float* w_t, float* dx, int32_t accumulate, bool res, const float* res_src,
+                     const float* res_mask, const unsigned char* res_mask8, void* workspace, dpft_stream_t stream, dpft::BnReduceFuse* fuse) {
     if (fuse) fuse->applied = false;
     int rc = check_desc(d);
     if (rc) return rc;
-    DPFT_REQUIRE(dy && w_t && dx, "conv dgrad: null tensor");
-    {
-        static const char* skip = getenv("DPFT_SKIP");      // timing experiments (see dpft_conv2d_nhwc_wgrad_f32)
-        if (skip && ((strstr(skip, "dgrad3x3") && d->kh == 3) || (strstr(skip, "dgrad1x1") && d->kh == 1)) && (int64_t)d->B * d->H * d->W >= 4096) {
-            if (fuse && fuse->sums) fuse->applied = true;
-            return DPFT_OK;
-        }
+    DPFT_REQUIRE(dy && w_t && dx && (!res || (res_src && res_mask)), "conv dgrad%s: null tensor", res ? " residual" : "");
+    if (skip_conv("dgrad3x3", "dgrad1x1", d->kh, (int64_t)d->B * d->H * d->W)) {
+        if (fuse && fuse->sums) fuse->applied = true;
+        return DPFT_OK;
     }
+    DPFT_REQUIRE(!res || (d->stride == 1 && !conv16_matches(d)), "conv dgrad residual: stride-1 bottleneck convs only");
     hipStream_t st = (hipStream_t)stream;
+    IgemmIn in;
+    in.ws = workspace != nullptr; in.accumulate = accumulate != 0; in.planes = d->a_planes && d->w_planes;
+    in.bnr = fuse && fuse->sums && (d->C & 3) == 0;
+    in.bnr_mask8 = res && fuse && fuse->mask8;
+    in.res_mask8 = res && res_mask8 && (d->C & 3) == 0;      // (the split-K reduction and the scalar tail read res_mask)
+    const IgemmPlan p = plan_igemm(d, res ? kDgradRes : kDgrad, in, plan_mode());
     ProfScope prof(1, d, st);
-    if (conv16_matches(d)) return conv16_dgrad(d, dy, w_t, dx, accumulate, st);
-    if (d->C <= 4 && d->K % 4 == 0 && (size_t)d->C * d->kh * d->kw * d->K * 4 <= 40960 && ((d->C * d->kh * d->kw * d->K) % 4) == 0) {
+    prof.family = p.family;
+    if (p.kernel == kConv16) return conv16_dgrad(d, dy, w_t, dx, accumulate, st);
+    if (p.kernel == kThin) {
         const size_t lds = (size_t)d->C * d->kh * d->kw * d->K * 4;
         const dim3 grid(cdiv((int64_t)d->B * d->H * d->W, 256));
 #define THIN_DGRAD(CI)                                                                                                  \
@@ -2033,137 +1718,56 @@ int dpft::conv_dgrad_fused(const dpft_conv_desc* d, const float* dy, const float
 #undef THIN_DGRAD
         return check_launch("conv dgrad (thin input)");
     }
-    IgemmArgs a; fill_igemm(a, d, true);
-    a.x = dy; a.w = w_t; a.y = dx; a.accumulate = accumulate;
-    a.x16 = a.y16 = d->act16 != 0;
-    a.w16 = d->act16 == 2;
-    if (d->a_planes && d->w_planes && !d->act16) { a.x3 = d->a_planes; a.w3 = d->w_planes; }
-    const bool fuse_ok = fuse && fuse->sums && (a.N & 3) == 0;
-    // Parity classes pay when each class fills the chip on its own (4x fewer MFMAs); on small maps (radar encoders) the
-    // stride^2 classes are stride^2 dependent launches of a few workgroups with the whole tap x channel loop inside
-    // (170 us for a 4x16x7 map) -- there one split-K launch over all taps is ~6x faster despite the wasted taps.
-    const int64_t class_wgs = (int64_t)cdiv((int64_t)a.B * cdiv(a.OH, d->stride) * cdiv(a.OW, d->stride), 64) * cdiv(a.N, 64);
-    if (d->stride > 1 && (a.C % BKV) == 0 && (class_wgs >= kNumCU / 2 || !workspace || d->act16)) {
+    IgemmArgs a;
+    if (p.kernel == kClasses) {
         // one launch per output-pixel parity class, each over the taps that can reach it (see IgemmArgs::sub_*)
-        const int sp = d->stride, cpt = a.C / BKV;
+        const int sp = d->stride;
+        DgradClass c;
         bool empty_class = false;
         for (int ph = 0; ph < sp; ++ph)
-            for (int pw = 0; pw < sp; ++pw) {
-                const int r0 = (ph + d->pad) % sp, s0 = (pw + d->pad) % sp;
-                if (r0 >= d->kh || s0 >= d->kw) empty_class = true;
-            }
+            for (int pw = 0; pw < sp; ++pw)
+                if (!dgrad_class(d, ph, pw, c) && (c.r0 >= d->kh || c.s0 >= d->kw)) empty_class = true;
         if (empty_class && !accumulate)      // pixels no tap reaches (1x1 stride-2: three of four) are plain zeros
-            DPFT_REQUIRE(zero_fill(dx, (d->act16 ? 2 : sizeof(float)) * (size_t)a.B * a.OH * a.OW * a.N, st) == DPFT_OK,
+            DPFT_REQUIRE(zero_fill(dx, (d->act16 ? 2 : sizeof(float)) * (size_t)d->B * d->H * d->W * d->C, st) == DPFT_OK,
                          "conv dgrad: zero fill failed");
+        in.bnr = in.bnr && !empty_class;      // classes partition the pixels: every pixel is added once
         for (int ph = 0; ph < sp; ++ph)
             for (int pw = 0; pw < sp; ++pw) {
-                const int r0 = (ph + d->pad) % sp, s0 = (pw + d->pad) % sp;
-                if (r0 >= d->kh || s0 >= d->kw || ph >= a.OH || pw >= a.OW) continue;
-                IgemmArgs q = a;
-                q.sub_step = sp; q.sub_ph = ph; q.sub_pw = pw;
-                q.sub_oh = (a.OH - ph + sp - 1) / sp; q.sub_ow = (a.OW - pw + sp - 1) / sp;
-                q.sub_r0 = r0; q.sub_s0 = s0;
-                q.sub_nr = (d->kh - r0 + sp - 1) / sp; q.sub_ns = (d->kw - s0 + sp - 1) / sp;
-                q.M = a.B * q.sub_oh * q.sub_ow;
-                q.ksteps = q.sub_nr * q.sub_ns * cpt;
-                TileChoice tq = choose_tile(q.M, q.N, q.C, q.ksteps);
-                tq.splits = 1;
-                if (fuse_ok && !empty_class) set_bnr(q, fuse);      // classes partition the pixels: every pixel is added once
-                rc = launch_igemm<true>(q, tq, false, st);
+                if (!dgrad_class(d, ph, pw, c)) continue;
+                in.M = c.M; in.ksteps = c.ksteps;
+                const IgemmPlan q = plan_igemm(d, kDgradClass, in, plan_mode());
+                fill_dgrad(a, d, q, dy, w_t, dx, workspace, fuse);
+                a.accumulate = accumulate;
+                a.sub_step = sp; a.sub_ph = ph; a.sub_pw = pw;
+                a.sub_oh = c.oh; a.sub_ow = c.ow; a.sub_r0 = c.r0; a.sub_s0 = c.s0; a.sub_nr = c.nr; a.sub_ns = c.ns;
+                a.M = c.M; a.ksteps = c.ksteps;
+                prof.family = q.family;
+                rc = launch_igemm<true>(a, q, false, st);
                 if (rc) return rc;
             }
-        if (fuse_ok && !empty_class) fuse->applied = true;
         return DPFT_OK;
     }
-    TileChoice t = choose_tile(a.M, a.N, a.C, a.ksteps, (d->act16 || d->stride > 1) ? 1 : taps_of(d));
-    const bool big16 = big16_tile(d, a, true, workspace != nullptr, t);
-    if (d->act16 && !big16) t.splits = 1;
-    if (big16 && t.splits > 1 && !sk_fixup_ok(a, t.splits, 2)) t.splits = 1;
-    bool fixup = false;
-    if (t.splits > 1) {
-        DPFT_REQUIRE(workspace, "conv dgrad: split-K selected but no workspace given");
-        a.partial = ws_slabs(workspace);
-        fixup = sk_fixup_ok(a, t.splits, 2);
-        if (fixup) a.sk_ticket = reinterpret_cast<int*>(workspace);
-    }
-    if ((t.splits == 1 || fixup) && fuse_ok) {      // (with the fix-up the last split workgroup of a tile runs the unsplit epilogue)
-        set_bnr(a, fuse);
-        fuse->applied = true;
-    }
-    // unsplit stride-1 launch that carries the reduction and nothing else in its epilogue: the reduction's operand (and mask
-    // byte) is requested with the first tile (EpiPrefetch mode 2; DPFT_EPF bit 1)
-    static const int epf_on = getenv("DPFT_EPF") == nullptr ? 3 : atoi(getenv("DPFT_EPF"));
-    if ((epf_on & 2) && t.splits == 1 && a.bnr_sums && !accumulate && d->stride == 1 && t.vec && (int64_t)a.M * a.N < (1ll << 29))
-        a.epf = 2;
-    rc = launch_igemm<true>(a, t, false, st);
-    if (rc) return rc;
-    if (t.splits > 1 && !fixup) {
-        const int64_t MN = (int64_t)a.M * a.N;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv(MN, 1024)), dim3(256), 0, st, a.partial, (const float*)nullptr, dx, MN, a.N, t.splits, accumulate);
-        rc = check_launch("conv dgrad split-K reduce");
-    }
-    return rc;
+    DPFT_REQUIRE(p.splits == 1 || workspace, "conv dgrad: split-K selected but no workspace given");
+    fill_dgrad(a, d, p, dy, w_t, dx, workspace, fuse);
+    a.accumulate = accumulate;
+    a.res_src = res_src; a.res_mask = res_mask;
+    if (in.res_mask8) a.res_mask8 = res_mask8;
+    rc = launch_igemm<true>(a, p, false, st);
+    if (rc || p.reduce == kReduceNone) return rc;
+    const int64_t MN = (int64_t)a.M * a.N;
+    if (res) hipLaunchKernelGGL(splitk_reduce_residual_kernel, dim3(cdiv(MN, 256)), dim3(256), 0, st, a.partial, res_src, res_mask, dx, MN, p.splits);
+    else hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv(MN, 1024)), dim3(256), 0, st, a.partial, (const float*)nullptr, dx, MN, a.N, p.splits, accumulate);
+    return check_launch("conv dgrad split-K reduce");
 }
 
-// dx = dgrad(dy) + (res_mask > 0 ? res_src : 0): stride-1 data gradient with the identity-branch ReLU backward folded
-// into the epilogue (internal: used by the ResNet launch plan)
+int dpft::conv_dgrad_fused(const dpft_conv_desc* d, const float* dy, const float* w_t, float* dx, int32_t accumulate,
+                           void* workspace, dpft_stream_t stream, BnReduceFuse* fuse) {
+    return dgrad_any(d, dy, w_t, dx, accumulate, false, nullptr, nullptr, nullptr, workspace, stream, fuse);
+}
 int dpft::conv_dgrad_residual(const dpft_conv_desc* d, const float* dy, const float* w_t, float* dx, const float* res_src,
                               const float* res_mask, void* workspace, dpft_stream_t stream, BnReduceFuse* fuse,
                               const unsigned char* res_mask8) {
-    if (fuse) fuse->applied = false;
-    int rc = check_desc(d);
-    if (rc) return rc;
-    DPFT_REQUIRE(dy && w_t && dx && res_src && res_mask, "conv dgrad residual: null tensor");
-    {
-        static const char* skip = getenv("DPFT_SKIP");      // timing experiments (see dpft_conv2d_nhwc_wgrad_f32)
-        if (skip && ((strstr(skip, "dgrad3x3") && d->kh == 3) || (strstr(skip, "dgrad1x1") && d->kh == 1)) && (int64_t)d->B * d->H * d->W >= 4096) {
-            if (fuse && fuse->sums) fuse->applied = true;
-            return DPFT_OK;
-        }
-    }
-
-    DPFT_REQUIRE(d->stride == 1 && !conv16_matches(d), "conv dgrad residual: stride-1 bottleneck convs only");
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope prof(1, d, st);
-    IgemmArgs a; fill_igemm(a, d, true);
-    a.x = dy; a.w = w_t; a.y = dx; a.res_src = res_src; a.res_mask = res_mask;
-    a.x16 = a.y16 = d->act16 != 0;
-    a.w16 = d->act16 == 2;
-    if (d->a_planes && d->w_planes && !d->act16) { a.x3 = d->a_planes; a.w3 = d->w_planes; }
-    if (res_mask8 && (a.N & 3) == 0) a.res_mask8 = res_mask8;      // (the split-K reduction and the scalar tail read res_mask)
-    TileChoice t = choose_tile(a.M, a.N, a.C, a.ksteps, d->act16 ? 1 : taps_of(d));
-    const bool big16 = big16_tile(d, a, true, workspace != nullptr, t);
-    if (d->act16 && !big16) t.splits = 1;
-    if (big16 && t.splits > 1 && !sk_fixup_ok(a, t.splits, 4)) t.splits = 1;
-    bool fixup = false;
-    if (t.splits > 1) {
-        DPFT_REQUIRE(workspace, "conv dgrad: split-K selected but no workspace given");
-        a.partial = ws_slabs(workspace);
-        fixup = sk_fixup_ok(a, t.splits, 4);
-        if (fixup) a.sk_ticket = reinterpret_cast<int*>(workspace);
-    }
-    if ((t.splits == 1 || fixup) && fuse && fuse->sums && (a.N & 3) == 0) {
-        set_bnr(a, fuse);
-        fuse->applied = true;
-    }
-    // the full form (identity gradient + next BatchNorm's reduction, both ReLU masks as bytes), unsplit, with enough rows to
-    // fill the chip with 128 x 64 tiles: its epilogue operands are fetched during the main loop (EpiPrefetch; the launcher
-    // takes the kernel when the operand types allow the pipelined path).  DPFT_EPF=0: the plain epilogue, A/B switch.
-    static const int epf_on = getenv("DPFT_EPF") == nullptr ? 3 : atoi(getenv("DPFT_EPF"));      // bit 0: this form, bit 1: mode 2
-    if ((epf_on & 1) && t.splits == 1 && a.bnr_sums && a.bnr_mask8 && a.res_mask8 && t.vec && (int64_t)a.M * a.N < (1ll << 29) &&
-        (int64_t)cdiv(a.M, 128) * cdiv(a.N, 64) >= kNumCU && getenv("DPFT_FORCE_TILE") == nullptr && !big16) {
-        a.epf = 1;
-        t.bm = 128; t.bn = 64;
-    }
-    rc = launch_igemm<true>(a, t, false, st);
-    if (rc) return rc;
-    if (t.splits > 1 && !fixup) {
-        const int64_t MN = (int64_t)a.M * a.N;
-        hipLaunchKernelGGL(splitk_reduce_residual_kernel, dim3(cdiv(MN, 256)), dim3(256), 0, st, a.partial, res_src,
-                           res_mask, dx, MN, t.splits);
-        rc = check_launch("conv dgrad split-K residual reduce");
-    }
-    return rc;
+    return dgrad_any(d, dy, w_t, dx, 0, true, res_src, res_mask, res_mask8, workspace, stream, fuse);
 }
 
 // C-ABI face of the launch plan's fused data gradients (kernel-level parity: tests/test_gpu_conv_table.py)
@@ -2186,25 +1790,17 @@ extern "C" int dpft_conv2d_nhwc_dgrad_bn_reduce_f32(const dpft_conv_desc* d, con
     return rc;
 }
 
-extern "C" int dpft_conv2d_nhwc_wgrad_f32(const dpft_conv_desc* d, const float* x, const float* dy,
-                                          const float* pro_bn, int32_t pro_relu, float* dw,
-                                          void* workspace, dpft_stream_t stream) {
-    {      // timing experiments (wrong gradients, DPFT_SKIP=...): the step time without a family = its cost on the critical path
-        static const char* skip = getenv("DPFT_SKIP");
-        if (skip && strstr(skip, "wgrad")) return DPFT_OK;
-    }
-    int rc = check_desc(d);
-    if (rc) return rc;
-    DPFT_REQUIRE(x && dy && dw, "conv wgrad: null tensor");
-    DPFT_REQUIRE(!pro_bn || ((d->C % 32 == 0) && (d->K % 4 == 0)),
-                 "conv wgrad: fused prologue needs C %% 32 == 0 and K %% 4 == 0 (C=%d, K=%d)", d->C, d->K);
-    hipStream_t st = (hipStream_t)stream;
+// the planned weight gradient; `db` (may be null): the bias gradient too, *bias_done tells whether the launch carried it
+static int launch_wgrad(const dpft_conv_desc* d, const float* x, const float* dy, const float* pro_bn, int32_t pro_relu, float* dw,
+                        float* db, bool* bias_done, void* workspace, hipStream_t st) {
+    const bool pro = pro_bn != nullptr;
+    WgradIn in;
+    in.ws = workspace != nullptr; in.pro = pro; in.pro_relu = pro_relu != 0; in.bias = db != nullptr;
+    const WgradPlan p = plan_wgrad(d, in, plan_mode());
     ProfScope prof(2, d, st);
-    if (!pro_bn) {
-        bool handled = false;
-        rc = thin_wgrad(d, x, dy, dw, workspace, st, handled);
-        if (rc || handled) return rc;
-    }
+    prof.family = p.family;
+    if (bias_done) *bias_done = p.reduce == kWgReduceSlabBias;
+    if (p.blocks) return thin_wgrad(d, p, x, dy, dw, db, workspace, st);
     WgradArgs a; memset(&a, 0, sizeof(a));
     a.x = x; a.dy = dy; a.dw = dw; a.pro = pro_bn; a.pro_relu = pro_relu;
     a.x16 = a.dy16 = d->act16 != 0;
@@ -2213,138 +1809,65 @@ extern "C" int dpft_conv2d_nhwc_wgrad_f32(const dpft_conv_desc* d, const float* 
     a.M = d->B * d->OH * d->OW;
     a.taps = d->kh * d->kw;
     a.J = a.taps * a.C;
-    const bool pro = pro_bn != nullptr;
-    const bool vec = (d->C % 32 == 0) && (d->K % 4 == 0);
-    a.psteps = cdiv(a.M, vec ? BKP : BK);
-    DPFT_REQUIRE(!vec || ((int64_t)a.M * a.K < (1ll << 29) && (int64_t)a.B * a.H * a.W * a.C < (1ll << 29)),
+    DPFT_REQUIRE(!p.vec || ((int64_t)a.M * a.K < (1ll << 29) && (int64_t)a.B * a.H * a.W * a.C < (1ll << 29)),
                  "conv wgrad: operand larger than 2 GiB");
-    int bmn, bnc;
-    int64_t tiles;
-    if (vec) {
-        if (d->K <= 32) { bmn = 32; bnc = 128; }
-        else if (d->K >= 128 && d->C >= 128 && (int64_t)cdiv(d->K, 128) * cdiv(d->C, 128) * a.taps >= 8) { bmn = 128; bnc = 128; }
-        else { bmn = 64; bnc = 64; }      // also when 128x128 would leave < 8 output tiles to split over
-        a.ktiles = cdiv(d->K, bmn);
-        a.ctiles = cdiv(d->C, bnc);
-        tiles = (int64_t)a.ktiles * a.ctiles * a.taps;
-    } else {
-        bmn = 64; bnc = 64;
-        a.ktiles = cdiv(d->K, 64);
-        a.ctiles = cdiv(a.J, 64);
-        tiles = (int64_t)a.ktiles * a.ctiles;
+    a.ktiles = p.ktiles; a.ctiles = p.ctiles; a.splits = p.splits;
+    a.psteps = cdiv(a.M, p.pk);
+    a.psteps_per_split = cdiv(a.psteps, p.splits);
+    a.partial = p.splits > 1 ? ws_slabs(workspace) : nullptr;
+    const dim3 grid((int)(p.tiles * p.splits)), block(256);
+    const size_t tbl = (size_t)a.psteps_per_split * p.pk * 4;      // pipelined forms: per-workgroup input-pixel offset table
+    switch (p.kernel) {
+    case kWgPipe16:
+        if (p.bmn == 128) launch_lds(wgrad_pipe16_kernel<128, 128, 2, 2, 64>, grid, block, (size_t)2 * 64 * (128 + 128) * 2 + tbl, st, a);
+        else launch_lds(wgrad_pipe16_kernel<64, 64, 2, 2, 128>, grid, block, (size_t)2 * 128 * (64 + 64) * 2 + tbl, st, a);
+        break;
+    case kWgX3: {
+        int rc = launch_wgrad_x3(a, pro, grid, st);
+        if (rc) return rc;
+        break;
     }
-    // Pixel-splits: the grid should be ONE full round of workgroups -- 256 for the 128x128 tile, 512 (two per CU) for
-    // the smaller ones -- and never spill a few workgroups into another round (tools/wgrad_sweep.sh: 36 tiles x 15
-    // splits = 540 workgroups ran 25 % slower than 36 x 14 = 504 or 36 x 7 = 252).  Partial slabs are bounded by
-    // 64 MiB (and by the workspace contract).
-    const int round_wgs = (vec && bmn == 128) ? kNumCU : kNumCU * 2;
-    int splits = (int)std::max<int64_t>(1, round_wgs / tiles);
-    {   // when one round would stay badly filled (e.g. 144 tiles), fill two rounds instead
-        const int s2 = (int)std::max<int64_t>(1, 2 * round_wgs / tiles);
-        const double f1 = (double)tiles * splits / round_wgs, f2 = (double)tiles * s2 / (2.0 * round_wgs);
-        if (f1 < 0.8 && f2 > f1 + 0.1) splits = s2;
-    }
-    const int64_t wbytes = (int64_t)d->K * a.J * 4;
-    const int max_splits = (int)std::max<int64_t>(1, std::min<int64_t>(512, (64ll << 20) / wbytes));
-    if (splits > max_splits) splits = max_splits;
-    if (splits > 1 && a.psteps / splits < 4) {
-        // Few pixels (radar encoders: 84 ... 1800): a workgroup would get under four pixel steps, so its fixed costs and
-        // the partial slabs decide.  tools/wgrad_small_sweep.sh: the 64x64 tile with about one workgroup per CU wins
-        // by 2-4x over fewer, fatter workgroups (448 pixels, 256->1024: 11.9 us vs 48.3 us unsplit 128x128 tiles).
-        if (vec && bmn == 128) {
-            bmn = 64; bnc = 64;
-            a.ktiles = cdiv(d->K, bmn); a.ctiles = cdiv(d->C, bnc);
-            tiles = (int64_t)a.ktiles * a.ctiles * a.taps;
-        }
-        splits = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(kNumCU / tiles, a.psteps), max_splits));
-    }
-    if (splits < 1) splits = 1;
-    if (const char* f = getenv("DPFT_FORCE_WGRAD")) {      // tuning aid: "tile,splits" (tile 128 | 64 for the vec kernel)
-        int tb, sp;
-        if (vec && sscanf(f, "%d,%d", &tb, &sp) == 2 && (tb == 128 || tb == 64)) {
-            bmn = tb; bnc = tb;
-            a.ktiles = cdiv(d->K, bmn); a.ctiles = cdiv(d->C, bnc);
-            tiles = (int64_t)a.ktiles * a.ctiles * a.taps;
-            splits = std::max(1, std::min(sp, max_splits));
-        }
-    }
-    if (splits > 1 && !workspace) splits = 1;
-    a.splits = splits;
-    a.psteps_per_split = cdiv(a.psteps, splits);
-    a.partial = splits > 1 ? ws_slabs(workspace) : nullptr;
-    const int nwg = (int)(tiles * splits);
-    dim3 grid(nwg), block(256);
-    static const int wpipe_env = getenv("DPFT_PIPE") ? atoi(getenv("DPFT_PIPE")) : 3;
-    static const int w16_env = getenv("DPFT_WGRAD16_PIPE") ? atoi(getenv("DPFT_WGRAD16_PIPE")) : 1;      // A/B switch
-    if (vec && d->act16 && !pro && w16_env && (bmn == 128 || bmn == 64) && (d->C % 8) == 0 && (d->K % 8) == 0) {
-        // both operands bf16 in memory, no prologue: LDS-DMA + transpose reads + bf16 MFMA (wgrad_pipe16_kernel)
-        const int pk = bmn == 128 ? 64 : 128;
-        a.psteps = cdiv(a.M, pk);
-        a.psteps_per_split = cdiv(a.psteps, splits);
-        const size_t lds = (size_t)2 * pk * (bmn + bnc) * 2 + (size_t)a.psteps_per_split * pk * 4;
-        g_prof_family = kFamBf16;
-        if (bmn == 128) launch_lds(wgrad_pipe16_kernel<128, 128, 2, 2, 64>, grid, block, lds, st, a);
-        else launch_lds(wgrad_pipe16_kernel<64, 64, 2, 2, 128>, grid, block, lds, st, a);
-    } else if (vec && (wpipe_env & 2) && g_conv_bf16 != 1 && !d->act16 && (!pro || pro_relu) && (bmn == 128 || bmn == 64)) {
-        // software-pipelined form (conv_pipe.h): psteps in units of its PK pixels
-        const int pk = bmn == 128 ? 32 : 64;
-        a.psteps = cdiv(a.M, pk);
-        a.psteps_per_split = cdiv(a.psteps, splits);
-        const size_t tbl = (size_t)a.psteps_per_split * pk * 4;      // per-workgroup input-pixel offset table
-        g_prof_family = kFamF32;
-        static const bool wx3 = getenv("DPFT_WGRAD_X3") == nullptr || atoi(getenv("DPFT_WGRAD_X3")) != 0;      // A/B switch
-        static const bool wx3_1x1 = getenv("DPFT_WGRAD_X3_1X1") == nullptr || atoi(getenv("DPFT_WGRAD_X3_1X1")) != 0;      // A/B switch
-        if (bmn == 128 && wx3 && split_on() && (a.taps > 1 || wx3_1x1) && 2.0 * a.M * (double)d->K * a.J >= 2e9) {
-            // the big multi-tap weight gradients on the split kernels (conv_x3.hip), like their forward / data gradient
-            g_prof_family = kFamX3;
-            rc = launch_wgrad_x3(a, pro, grid, st);
-            if (rc) return rc;
-        } else if (bmn == 128) {
-            const size_t lds = (size_t)2 * 32 * (128 + 128) * 4 + tbl;
-            if (pro) launch_lds(wgrad_pipe_kernel<128, 128, 2, 2, 32, true>, grid, block, lds, st, a);
-            else launch_lds(wgrad_pipe_kernel<128, 128, 2, 2, 32, false>, grid, block, lds, st, a);
-        } else {
-            const size_t lds = (size_t)2 * 64 * (64 + 64) * 4 + tbl;
-            if (pro) launch_lds(wgrad_pipe_kernel<64, 64, 2, 2, 64, true>, grid, block, lds, st, a);
-            else launch_lds(wgrad_pipe_kernel<64, 64, 2, 2, 64, false>, grid, block, lds, st, a);
-        }
-    } else if (vec) {
-        g_prof_family = g_conv_bf16 == 1 && (bmn == 128 || bmn == 64) ? kFamBf16 : kFamF32;
-#define LAUNCH_WG(BM_, BN_, WGM_, WGN_)                                                           \
+    case kWgPipe:
+        if (p.bmn == 128 && pro) launch_lds(wgrad_pipe_kernel<128, 128, 2, 2, 32, true>, grid, block, (size_t)2 * 32 * (128 + 128) * 4 + tbl, st, a);
+        else if (p.bmn == 128) launch_lds(wgrad_pipe_kernel<128, 128, 2, 2, 32, false>, grid, block, (size_t)2 * 32 * (128 + 128) * 4 + tbl, st, a);
+        else if (pro) launch_lds(wgrad_pipe_kernel<64, 64, 2, 2, 64, true>, grid, block, (size_t)2 * 64 * (64 + 64) * 4 + tbl, st, a);
+        else launch_lds(wgrad_pipe_kernel<64, 64, 2, 2, 64, false>, grid, block, (size_t)2 * 64 * (64 + 64) * 4 + tbl, st, a);
+        break;
+    case kWgVec:
+#define LAUNCH_WG(BM_, BN_, WGM_, WGN_, B16_)                                                           \
     do {                                                                                          \
-        if (pro) hipLaunchKernelGGL((wgrad_vec_kernel<BM_, BN_, WGM_, WGN_, true>), grid, block, 0, st, a);  \
-        else hipLaunchKernelGGL((wgrad_vec_kernel<BM_, BN_, WGM_, WGN_, false>), grid, block, 0, st, a);     \
+        if (pro) hipLaunchKernelGGL((wgrad_vec_kernel<BM_, BN_, WGM_, WGN_, true, B16_>), grid, block, 0, st, a);  \
+        else hipLaunchKernelGGL((wgrad_vec_kernel<BM_, BN_, WGM_, WGN_, false, B16_>), grid, block, 0, st, a);     \
     } while (0)
-        if (bmn == 128 && g_conv_bf16 == 1) {      // mixed-precision mode (dpft_conv_set_compute): bf16 operands
-            if (pro) hipLaunchKernelGGL((wgrad_vec_kernel<128, 128, 2, 2, true, true>), grid, block, 0, st, a);
-            else hipLaunchKernelGGL((wgrad_vec_kernel<128, 128, 2, 2, false, true>), grid, block, 0, st, a);
-        } else if (bmn == 64 && g_conv_bf16 == 1) {
-            if (pro) hipLaunchKernelGGL((wgrad_vec_kernel<64, 64, 2, 2, true, true>), grid, block, 0, st, a);
-            else hipLaunchKernelGGL((wgrad_vec_kernel<64, 64, 2, 2, false, true>), grid, block, 0, st, a);
-        } else if (bmn == 128) LAUNCH_WG(128, 128, 2, 2);
-        else if (bmn == 64) LAUNCH_WG(64, 64, 2, 2);
-        else LAUNCH_WG(32, 128, 1, 4);
+        if (p.bmn == 128 && p.family == kFamBf16) LAUNCH_WG(128, 128, 2, 2, true);      // mixed-precision mode: bf16 operands
+        else if (p.bmn == 64 && p.family == kFamBf16) LAUNCH_WG(64, 64, 2, 2, true);
+        else if (p.bmn == 128) LAUNCH_WG(128, 128, 2, 2, false);
+        else if (p.bmn == 64) LAUNCH_WG(64, 64, 2, 2, false);
+        else LAUNCH_WG(32, 128, 1, 4, false);
 #undef LAUNCH_WG
-    } else {
+        break;
+    default:
         hipLaunchKernelGGL(wgrad_gen_kernel, grid, block, 0, st, a);
     }
-    rc = check_launch("conv wgrad");
+    int rc = check_launch("conv wgrad");
+    if (rc || p.reduce == kWgReduceNone || skip_family("wreduce")) return rc;      // (wreduce: the reduction launches' cost on the critical path)
+    const int64_t n = (int64_t)d->K * a.J;
+    if (p.reduce == kWgReduceWide16) hipLaunchKernelGGL(splitk_reduce_wide_kernel<16>, dim3(cdiv(n / 4, 16)), dim3(256), 0, st, a.partial, dw, n, p.splits);
+    else if (p.reduce == kWgReduceWide4) hipLaunchKernelGGL(splitk_reduce_wide_kernel<4>, dim3(cdiv(n / 4, 64)), dim3(256), 0, st, a.partial, dw, n, p.splits);
+    else hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv(n, 1024)), dim3(256), 0, st, a.partial, (const float*)nullptr, dw, n, 4, p.splits, 0);
+    return check_launch("conv wgrad split-K reduce");
+}
+
+extern "C" int dpft_conv2d_nhwc_wgrad_f32(const dpft_conv_desc* d, const float* x, const float* dy,
+                                          const float* pro_bn, int32_t pro_relu, float* dw,
+                                          void* workspace, dpft_stream_t stream) {
+    if (skip_family("wgrad")) return DPFT_OK;
+    int rc = check_desc(d);
     if (rc) return rc;
-    {
-        static const char* skip = getenv("DPFT_SKIP");      // timing experiment: the reduction launches' cost on the critical path
-        if (skip && strstr(skip, "wreduce")) return rc;
-    }
-    if (splits > 1) {
-        const int64_t n = (int64_t)d->K * a.J;
-        if ((n & 3) == 0 && splits >= 16) {
-            if (n / 4 <= (int64_t)kNumCU * 64) hipLaunchKernelGGL(splitk_reduce_wide_kernel<16>, dim3(cdiv(n / 4, 16)), dim3(256), 0, st, a.partial, dw, n, splits);
-            else hipLaunchKernelGGL(splitk_reduce_wide_kernel<4>, dim3(cdiv(n / 4, 64)), dim3(256), 0, st, a.partial, dw, n, splits);
-        } else {
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv(n, 1024)), dim3(256), 0, st, a.partial, (const float*)nullptr, dw, n, 4, splits, 0);
-        }
-        rc = check_launch("conv wgrad split-K reduce");
-    }
-    return rc;
+    DPFT_REQUIRE(x && dy && dw, "conv wgrad: null tensor");
+    DPFT_REQUIRE(!pro_bn || ((d->C % 32 == 0) && (d->K % 4 == 0)),
+                 "conv wgrad: fused prologue needs C %% 32 == 0 and K %% 4 == 0 (C=%d, K=%d)", d->C, d->K);
+    return launch_wgrad(d, x, dy, pro_bn, pro_relu, dw, nullptr, nullptr, workspace, (hipStream_t)stream);
 }
 
 extern "C" int dpft_weight_transpose_f32(const float* w, float* w_t, int32_t K, int32_t taps,
@@ -2410,8 +1933,7 @@ extern "C" int dpft_bias_grad_f32(const float* dy, float* db, int64_t M, int32_t
 // bias gradient behind a weight gradient on the same stream: the conv workspace is free again (ticket header zero, slabs
 // consumed) -- the slab form above; without a workspace the cleared-output + atomics form
 int dpft::bias_grad_ws(const float* dy, float* db, int64_t M, int32_t K, void* workspace, dpft_stream_t stream) {
-    static const bool slab_on = getenv("DPFT_BIAS_SLAB") == nullptr || atoi(getenv("DPFT_BIAS_SLAB")) != 0;      // A/B switch
-    if (!workspace || !slab_on || K > 256 || K <= 0) return dpft_bias_grad_f32(dy, db, M, K, stream);
+    if (!workspace || !tuning().bias_slab || K > 256 || K <= 0) return dpft_bias_grad_f32(dy, db, M, K, stream);
     const int rpi = 256 / K;
     const int blocks = (int)std::min<int64_t>(kBiasBlocks, (M + rpi - 1) / rpi);
     hipLaunchKernelGGL(bias_grad_slab_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dy, db, M, (int)K, ws_slabs(workspace),
@@ -2426,19 +1948,11 @@ extern "C" int dpft_conv2d_nhwc_wgrad_bias_f32(const dpft_conv_desc* d, const fl
     int rc = check_desc(d);
     if (rc) return rc;
     DPFT_REQUIRE(x && dy && dw && db, "conv wgrad_bias: null tensor");
-    static const bool fuse = getenv("DPFT_BIAS_FUSE") == nullptr || atoi(getenv("DPFT_BIAS_FUSE")) != 0;      // A/B switch
-    const bool fusable = dpft::conv16_matches(d) ||
-                         (d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad == 0 && d->K == 16 && (d->C == 3 || d->C == 6));
-    if (fuse && fusable && workspace && !d->act16) {
-        dpft::ProfScope prof(2, d, (hipStream_t)stream);
-        bool handled = false, bias_done = false;
-        rc = dpft::thin_wgrad(d, x, dy, dw, workspace, (hipStream_t)stream, handled, db, &bias_done);
-        if (rc) return rc;
-        if (handled && bias_done) return DPFT_OK;
-        if (handled) return dpft::bias_grad_ws(dy, db, (int64_t)d->B * d->OH * d->OW, d->K, workspace, stream);
-    }
-    rc = dpft_conv2d_nhwc_wgrad_f32(d, x, dy, nullptr, 0, dw, workspace, stream);
-    if (rc) return rc;
+    // the thin kernels that have dy at hand (3x3 16 -> 16, thin 1x1 -> 16) carry the bias gradient (DPFT_SKIP=wgrad leaves them in)
+    const bool fuse = tuning().bias_fuse && workspace && !d->act16 && (conv16_matches(d) || conv1x1_to16_top_matches(d));
+    bool bias_done = false;
+    if (fuse || !skip_family("wgrad")) rc = launch_wgrad(d, x, dy, nullptr, 0, dw, fuse ? db : nullptr, &bias_done, workspace, (hipStream_t)stream);
+    if (rc || bias_done) return rc;
     return dpft::bias_grad_ws(dy, db, (int64_t)d->B * d->OH * d->OW, d->K, workspace, stream);
 }
 

@@ -13,6 +13,7 @@
 //   wgrad1x1_small_kernel   : K <= 16, C <= 8 (raw-input laterals, the 6->3 radar adjustment): pure streaming.
 #pragma once
 #include "common.h"
+#include "conv_plan.h"      // the tile constants and the shape matchers (host only)
 
 namespace dpft {
 
@@ -29,7 +30,6 @@ struct Conv16Args {
     const float* pos_y;  // embedding, embeddings/sinusoidal.py: the reference's two fp32 adds in their order)
 };
 
-constexpr int T16H = 8, T16W = 32;
 
 template <bool FLIP>
 __global__ __launch_bounds__(256) void conv16_3x3_kernel(Conv16Args a) {
@@ -302,7 +302,7 @@ struct WgradStemArgs {
     int tiles_w, tiles_h, total_tiles;
 };
 
-constexpr int STEM_OH = 4, STEM_OW = 16, STEM_IH = 2 * STEM_OH + 5, STEM_IW = 2 * STEM_OW + 5, STEM_ROW = 112;
+constexpr int STEM_IH = 2 * STEM_OH + 5, STEM_IW = 2 * STEM_OW + 5, STEM_ROW = 112;
 
 __global__ __launch_bounds__(256) void wgrad_stem7_kernel(WgradStemArgs a) {
     constexpr int XN = STEM_IH * STEM_ROW;             // x tile floats (rows padded 111 -> 112)
@@ -432,13 +432,6 @@ __global__ __launch_bounds__(256) void wgrad_stem7_kernel(WgradStemArgs a) {
     }
 }
 
-static bool wgrad_stem7_matches(const dpft_conv_desc* d) {
-    // (each block ends with a 3-round wave reduction and a 37 KB slab: worth it from ~8 tiles per block on -- the radar stems,
-    // 27 k output pixels, stay with the generic kernel: 26.6 vs 37.0 us)
-    return d->kh == 7 && d->kw == 7 && d->stride == 2 && d->pad == 3 && d->C == 3 && d->K == 64 && !d->act16 &&
-           (int64_t)d->B * d->OH * d->OW >= 131072;
-}
-
 // 1x1 weight gradient with very few channels: dW[k][c] = sum_p dy[p][k] * x[p][c]; one thread walks a pixel stripe
 template <int K, int C>
 __global__ __launch_bounds__(256) void wgrad1x1_small_kernel(const float* __restrict__ x, const float* __restrict__ dy,
@@ -563,10 +556,6 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
 
 // ---- host side: called by the generic conv entry points (conv.hip) when the shape matches --------------------
 
-static bool conv16_matches(const dpft_conv_desc* d) {
-    return d->C == 16 && d->K == 16 && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1;
-}
-
 // 1x1 forward with very few input channels and 16 outputs (the FPN lateral on the raw-input level: 3 -> 16 over
 // 4 x 512 x 910 pixels, 6 -> 16 on the radar maps): pure streaming, 4 C bytes in and 64 bytes out per pixel.  The generic
 // implicit-GEMM path pads to a 32-wide tile and gathers scalars (92 us = 1.5 TB/s on the camera level); here 4 lanes share
@@ -612,12 +601,6 @@ __global__ __launch_bounds__(256) void conv1x1_to16_kernel(const float* __restri
     }
 }
 
-static bool conv1x1_to16_matches(const dpft_conv_desc* d) {
-    // (below ~256 k pixels the launch is latency-sized and the generic path is as fast: radar laterals 13.1 vs 14.6 us)
-    return d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad == 0 && d->K == 16 && (d->C == 3 || d->C == 6) && !d->act16 &&
-           (int64_t)d->B * d->H * d->W >= 262144;
-}
-
 static int conv1x1_to16_forward(const dpft_conv_desc* d, const float* x, const float* w, const float* bias, float* y, hipStream_t st) {
     const long M = (long)d->B * d->H * d->W;
     const int blocks = (int)std::max<long>(1, std::min<long>(kNumCU * 16, (M + 63) / 64));
@@ -627,9 +610,6 @@ static int conv1x1_to16_forward(const dpft_conv_desc* d, const float* x, const f
 }
 
 // the lateral of a raw-input level with the top-down add in its epilogue (any map size: it replaces two launches)
-static bool conv1x1_to16_top_matches(const dpft_conv_desc* d) {
-    return d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad == 0 && d->K == 16 && (d->C == 3 || d->C == 6) && !d->act16;
-}
 static int conv1x1_to16_top_forward(const dpft_conv_desc* d, const float* x, const float* w, const float* bias, const float* top, int TH,
                                     int TW, float* y, hipStream_t st) {
     const long M = (long)d->B * d->H * d->W;
@@ -653,15 +633,6 @@ static int conv16_dgrad(const dpft_conv_desc* d, const float* dy, const float* w
     dim3 grid(cdiv(d->W, T16W), cdiv(d->H, T16H), d->B);
     hipLaunchKernelGGL(conv16_3x3_kernel<true>, grid, dim3(256), 0, st, a);
     return check_launch("conv16 dgrad");
-}
-
-static int conv16_wgrad_blocks(const dpft_conv_desc* d) {      // streaming form; also the workspace bound of both forms
-    const long groups = (long)d->B * d->H * cdiv(d->W, 4);
-    return (int)std::max<long>(1, std::min<long>(kNumCU * 4, groups / 64));
-}
-static int conv16_wgrad_tiled_blocks(const dpft_conv_desc* d) {
-    const long tiles = (long)d->B * cdiv(d->H, T16H) * cdiv(d->W, T16W);
-    return (int)std::max<long>(1, std::min<long>(std::min<long>(kNumCU * 4, conv16_wgrad_blocks(d)), tiles));
 }
 
 }  // namespace dpft

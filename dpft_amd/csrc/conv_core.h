@@ -3,6 +3,7 @@
 // the tile decoder.  Moved out of conv.hip in round 5 so that the 3 x bf16 split kernels build as their own translation unit.
 #pragma once
 #include "common.h"
+#include "conv_plan.h"      // BK, BKV, BKP, the launch plans (host only)
 
 #include <math.h>
 #include <stdlib.h>
@@ -14,15 +15,11 @@
 
 namespace dpft {
 
-constexpr int BK = 32;        // generic path K-step
-constexpr int BKV = 64;       // vector path K-step: one barrier pair per 2048+ MFMA cycles, and the register
-                              // prefetch of the next step has that long to land (HBM/L2 latency under load)
 constexpr int LDK = BKV + 4;  // vector path: padded LDS row (272 B = 17 x 16 B: odd slot stride, conflict-free b128)
 constexpr int LDKH = BKV + 8; // bf16 tiles (mixed-precision mode): 144-byte rows
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int LDG = BK + 1;   // generic path: odd pad, ds_read_b32 fragments
-constexpr int BKP = 64;       // wgrad vector path: pixels per step
 
 // Activation tensors may live in HBM as bf16 (dpft_conv_desc.act16: mixed-precision storage of BASELINE.json configs[4]).
 // A loader lane still owns 4 consecutive channels: 8 bytes instead of 16.  Offsets keep their fp32 (x 4 bytes) form and
@@ -544,7 +541,6 @@ struct WgradArgs {
 int launch_igemm_x3(IgemmArgs& a, int bm, int bn, bool dgrad, bool pro, hipStream_t st);
 int split_planes(const float* src, void* dst, int64_t n, hipStream_t st);
 // conv_stream.hip: 1x1 convs with 64 / 128 input channels and K % 256 == 0 on large maps (weights in LDS, rows private to a wave)
-bool stream1x1_match(const dpft_conv_desc* d, int* tile_rows);
 int launch_stream1x1(const dpft_conv_desc* d, const float* x, const float* w, const float* pro_bn, float* y, float* stats,
                      const float* out_bn, const float* residual, int relu, hipStream_t st, unsigned long long* bns = nullptr,
                      const BnSumsRef* pro_sums = nullptr);

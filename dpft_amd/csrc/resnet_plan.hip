@@ -387,15 +387,13 @@ static int conv_bn_train(ResnetPlan* p, const Tables& T, const ConvRef& c, int b
     if (p->frozen)      // the BN block comes from the running statistics (eval_bn_blocks): no statistics, no finalize
         return conv_fwd_sums(&c.d, x, w, nullptr, pro, pro ? 1 : 0, y, nullptr, ws, st);
     unsigned long long* sums = bn_sums_on(p) ? (unsigned long long*)(A + p->o_bnacc + p->bnacc[bn]) : nullptr;
-    bool sums_used = false, launched = false;
+    bool sums_used = false, used = false;
+    BnSumsRef ps{};      // the prologue's BatchNorm as column sums, where the layer is still pending and this conv's kernel takes them
     if (sums && pro && pro_bn >= 0 && p->bn_pending[pro_bn]) {
-        const BnSumsRef ps = bn_sums_ref(p, T, A, pro_bn, pro_K, pro_M);
-        bool used = false;
-        RC(conv_fwd_sums(&c.d, x, w, nullptr, pro, 1, y, stats, ws, st, sums, &sums_used, &ps, &used));
-        launched = used;
-        if (!used) RC(bn_finalize_one(p, T, A, pro_bn, st));      // this conv's kernel reads BN blocks only
+        if (conv_fwd_pro_from_sums(&c.d)) ps = bn_sums_ref(p, T, A, pro_bn, pro_K, pro_M);
+        else RC(bn_finalize_one(p, T, A, pro_bn, st));      // this conv's kernel reads BN blocks only
     }
-    if (!launched) RC(conv_fwd_sums(&c.d, x, w, nullptr, pro, pro ? 1 : 0, y, stats, ws, st, sums, &sums_used));
+    RC(conv_fwd_sums(&c.d, x, w, nullptr, pro, pro ? 1 : 0, y, stats, ws, st, sums, &sums_used, &ps, &used));
     if (sums_used) {
         p->bn_pending[bn] = 1;
         p->pend_list.push_back(ResnetPlan::PendingBn{bn, c.d.K, (long long)M, (size_t)(bnp - A)});

@@ -93,6 +93,12 @@ int dpft_split_planes_f32(const float* src, void* planes, int64_t n, dpft_stream
  * *tile_rows receives the tile height so the caller can recover per-tile counts. */
 int32_t dpft_conv2d_stats_tiles(const dpft_conv_desc* d, int32_t* tile_rows);
 
+/* The kernel family (numbering of dpft_profile_get_family) the launch plan names for this problem in the current compute mode:
+ * kind 0 forward, 1 data gradient, 2 weight gradient; has_workspace as the launch would be given one.  For a strided data
+ * gradient run as parity classes: the family of the last class that launches (what its profile record holds).  Decided on the
+ * host from the descriptor alone -- nothing is launched; -1 on a bad descriptor or kind. */
+int32_t dpft_conv2d_planned_family(const dpft_conv_desc* d, int32_t kind, int32_t has_workspace);
+
 /* Arithmetic of the forward / data-gradient GEMMs of every conv with C % 64 == 0 and of the 128 x 128-tiled weight
  * gradients (process-wide; call between launches):
  *   0  fp32 operands, fp32 accumulation -- the reference's arithmetic (config/kradar.json "dtype": "float32"), default;

@@ -297,8 +297,18 @@ def build_lattice():
 
 
 LATTICE = build_lattice()
+# the compute modes (ops.conv_set_compute name, split switch), the forced tiles and the case lists they run on -- shared by the
+# host test of the launch plan (tests/test_conv_lattice.py) and the GPU tests (tests/test_gpu_conv_geometry.py)
+MODES = {"fp32": ("fp32", False), "fp32+split": ("fp32", True), "bf16x3": ("bf16x3", True), "bf16": ("bf16", True)}
+FORCE_TILES = ["128,128,1", "128,64,2", "64,128,1", "64,64,3"]
+FORCE_WGRADS = ["128,1", "128,3", "64,1", "64,5"]
 BNACT = "dpft_conv2d_nhwc_fwd_bnact_f32"
 WGRAD_PRO = "dpft_conv2d_nhwc_wgrad_f32 + prologue"
+
+
+# (of the large cases one goes through the forced tiles: a strided data gradient that takes the parity classes WITH a workspace)
+C64 = [c for c in LATTICE if c.cls == "c64" and (c.name not in LARGE_NAMES or c.name == "classes-s3-2x2-c192")]
+WVEC = [c for c in LATTICE if c.C % 32 == 0 and c.K % 4 == 0 and c.name not in LARGE_NAMES]
 
 
 def refusal(c, entry):

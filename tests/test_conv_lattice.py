@@ -148,6 +148,84 @@ def test_refused_geometries_are_refused_through_the_cabi():
     assert not any(L.refusal(c, "dpft_conv2d_nhwc_fwd_f32") for c in L.LATTICE)
 
 
+FAMILY = {0: "f32", 1: "x3", 2: "bf16", 3: "vector"}      # dpft_profile_get_family's numbering
+KINDS = {"fwd": 0, "dgrad": 1, "wgrad": 2}
+COMPUTE = {"fp32": 0, "bf16": 1, "bf16x3": 2}
+
+
+def _planned(lib, c, kind, workspace=True):
+    from dpft_amd.hip.lib import make_desc
+    d = make_desc(c.B, c.H, c.W, c.C, c.K, c.kh, c.kw, c.stride, c.pad)
+    fam = int(lib.dpft_conv2d_planned_family(C.byref(d), KINDS[kind], int(workspace)))
+    assert fam in FAMILY, (c, kind, fam)
+    return FAMILY[fam]
+
+
+@pytest.fixture
+def plan_mode():
+    """Sets the compute mode and the split switch as the GPU tests' compute_mode() does; puts both back."""
+    from dpft_amd.hip.lib import lib
+    was = int(lib.dpft_conv_get_compute()), int(lib.dpft_conv_get_split())
+
+    def set_mode(name):
+        compute, split = L.MODES[name]
+        assert lib.dpft_conv_set_compute(COMPUTE[compute]) == 0 and lib.dpft_conv_set_split(int(split)) == 0
+        return lib
+    yield set_mode
+    lib.dpft_conv_set_compute(was[0])
+    lib.dpft_conv_set_split(was[1])
+
+
+@pytest.mark.parametrize("mode", list(L.MODES))
+def test_planned_family_is_the_expected_family_on_the_lattice(mode, plan_mode):
+    """What the launch plan names (dpft_conv2d_planned_family, host only) equals conv_lattice.expected_family for every case,
+    kind and mode -- tests/test_gpu_conv_geometry.py asserts the same restatement against what RAN, so the plan is what runs."""
+    lib = plan_mode(mode)
+    bad = []
+    for c in L.LATTICE:
+        for kind in KINDS:
+            got, want = _planned(lib, c, kind), L.expected_family(c, kind, mode)
+            if got != want:
+                bad.append((c.name, kind, got, want))
+        if c.stride > 1 and c.K % 64 == 0 and c.C > 4:      # run_case: the strided data gradient without a workspace
+            got, want = _planned(lib, c, "dgrad", workspace=False), L.expected_family(c, "dgrad", mode, workspace=False)
+            if got != want:
+                bad.append((c.name, "dgrad, no workspace", got, want))
+    assert lib.dpft_conv2d_planned_family(None, 0, 1) == -1
+    assert not bad, (mode, bad)
+
+
+def test_planned_family_under_forced_tiles(plan_mode, monkeypatch):
+    """Every entry of FORCE_TILES / FORCE_WGRADS on the case lists and modes of the GPU tests that force them."""
+    C64, FORCE_TILES, FORCE_WGRADS, WVEC = L.C64, L.FORCE_TILES, L.FORCE_WGRADS, L.WVEC
+    bad = []
+    for tile in FORCE_TILES:
+        monkeypatch.setenv("DPFT_FORCE_TILE", tile)
+        t = tuple(int(v) for v in tile.split(","))
+        for mode in ("fp32", "bf16x3", "bf16"):
+            lib = plan_mode(mode)
+            for c in C64:
+                for kind in ("fwd", "dgrad"):
+                    got, want = _planned(lib, c, kind), L.expected_family(c, kind, mode, t)
+                    if got != want:
+                        bad.append((tile, mode, c.name, kind, got, want))
+                if c.stride > 1 and c.K % 64 == 0:
+                    got, want = _planned(lib, c, "dgrad", workspace=False), L.expected_family(c, "dgrad", mode, t, workspace=False)
+                    if got != want:
+                        bad.append((tile, mode, c.name, "dgrad, no workspace", got, want))
+    monkeypatch.delenv("DPFT_FORCE_TILE")
+    for wtile in FORCE_WGRADS:
+        monkeypatch.setenv("DPFT_FORCE_WGRAD", wtile)
+        wt = tuple(int(v) for v in wtile.split(","))
+        for mode in ("fp32", "bf16"):
+            lib = plan_mode(mode)
+            for c in WVEC:
+                got, want = _planned(lib, c, "wgrad"), L.expected_family(c, "wgrad", mode, wtile=wt)
+                if got != want:
+                    bad.append((wtile, mode, c.name, "wgrad", got, want))
+    assert not bad, bad
+
+
 @pytest.mark.parametrize("split", [0, 1])
 def test_sizing_and_tiling_answers_for_every_case(split):
     from dpft_amd.hip.lib import lib, make_desc

@@ -19,13 +19,8 @@ from tests import conv_lattice as L
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
-MODES = {"fp32": ("fp32", False), "fp32+split": ("fp32", True), "bf16x3": ("bf16x3", True), "bf16": ("bf16", True)}
-FORCE_TILES = ["128,128,1", "128,64,2", "64,128,1", "64,64,3"]
-FORCE_WGRADS = ["128,1", "128,3", "64,1", "64,5"]
-CASES = list(L.LATTICE)
-# (of the large cases one goes through the forced tiles: a strided data gradient that takes the parity classes WITH a workspace)
-C64 = [c for c in CASES if c.cls == "c64" and (c.name not in L.LARGE_NAMES or c.name == "classes-s3-2x2-c192")]
-WVEC = [c for c in CASES if c.C % 32 == 0 and c.K % 4 == 0 and c.name not in L.LARGE_NAMES]
+MODES, FORCE_TILES, FORCE_WGRADS = L.MODES, L.FORCE_TILES, L.FORCE_WGRADS      # (shared with the host test of the launch plan)
+CASES, C64, WVEC = list(L.LATTICE), L.C64, L.WVEC
 _ids = lambda cs: [c.name for c in cs]
 
 
