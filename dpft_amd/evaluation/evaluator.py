@@ -1,7 +1,8 @@
 """Data-parallel evaluation loop: the counterpart of ``CentralizedEvaluator`` (src/dprt/evaluation/evaluator.py:19-214) on this
 package's device-side pieces.
 
-``evaluate_one_epoch`` (evaluator.py:138-177) = eval-mode forward -> ``Metric`` (two launches per batch) -> exporter (one
+``evaluate_one_epoch`` (evaluator.py:138-177) = eval-mode forward -> [``RotatedNMS``, only with ``evaluate.nms`` set: three
+launches per batch, nms.py] -> ``Metric`` (two launches per batch) -> exporter (one
 selection launch per batch and threshold chunk) for every batch of the test split.  Under ``torch.distributed`` every rank
 takes a CONTIGUOUS block of the split (``BlockShardedSampler``: sample k keeps the file name it has in a one-process run),
 exports into a private root, and rank 0 merges the rank trees afterwards: numbered files are moved, the appended ``val.txt``
@@ -58,11 +59,14 @@ class DataParallelEvaluator:
     latency_reps, latency_warmup = 300, 10      # evaluator.py:110,114
 
     def __init__(self, metric: Optional[torch.nn.Module] = None, exporter: Optional[Callable] = None,
-                 device: Optional[torch.device] = None, logging: Optional[str] = None, dataset_ap=None):
+                 device: Optional[torch.device] = None, logging: Optional[str] = None, dataset_ap=None, nms=None):
         """``logging``: None, 'step' or 'epoch' (evaluator.py:24-28).  ``dataset_ap``: an optional
-        ``dpft_amd.evaluation.dataset_ap.DatasetAP`` -- split-level AP_BEV / AP_3D accumulated beside the per-step metrics."""
+        ``dpft_amd.evaluation.dataset_ap.DatasetAP`` -- split-level AP_BEV / AP_3D accumulated beside the per-step metrics.
+        ``nms``: an optional ``dpft_amd.evaluation.nms.RotatedNMS`` -- the metric, the split-level AP and the exporter then read
+        ``nms.suppress(output)`` instead of the model's raw output (not in the reference: its numbers and files differ)."""
         self.eval_fn, self.export_fn, self.logging = metric, exporter, logging
         self.dataset_ap = dataset_ap
+        self.nms = nms
         self.device = torch.device(device) if device is not None else torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
         self.rank = dist.get_rank() if dist.is_initialized() else 0
         self.world = dist.get_world_size() if dist.is_initialized() else 1
@@ -74,10 +78,15 @@ class DataParallelEvaluator:
         if device.type == "cuda" and device.index is None:
             device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
         from dpft_amd.evaluation.dataset_ap import DatasetAP
+        nms = None
+        if config.get("evaluate", {}).get("nms"):                 # (absent or false: nothing is imported or built)
+            from dpft_amd.evaluation.nms import RotatedNMS
+            nms = RotatedNMS.from_config(config)
         return cls(metric=build_metric(config["evaluate"]),
                    exporter=build_exporter(config["evaluate"]["exporter"]["name"], config),
                    device=device, logging=config["train"].get("logging"),
-                   dataset_ap=DatasetAP.from_config(config))      # (None unless evaluate.dataset_ap is set)
+                   dataset_ap=DatasetAP.from_config(config),      # (None unless evaluate.dataset_ap is set)
+                   nms=nms)
 
     def __call__(self, *args, **kwargs):
         return self.evaluate(*args, **kwargs)
@@ -126,6 +135,8 @@ class DataParallelEvaluator:
             labels = [self._dict_to(l) for l in labels]
             data = self._dict_to(data)
             output = model(data)
+            if self.nms is not None:                    # duplicates read as background to all three consumers below
+                output = self.nms.suppress(output)
             metrics = self.eval_fn(output, labels) if self.eval_fn is not None else {}
             if self.logging == "step" and rank == 0:
                 self.log_scalars(writer, metrics, i + epoch * n_steps, "test")

@@ -210,6 +210,12 @@ class DataParallelTrainer:
         if config.get("evaluate", {}).get("dataset_ap"):
             from dpft_amd.evaluation.dataset_ap import DatasetAP
             self.dataset_ap = DatasetAP.from_config(config)
+        # optional rotated NMS in front of the validation metric and the split-level AP (evaluate.nms; evaluation/nms.py); the
+        # training step and the validation loss always read the raw output
+        self.nms = None
+        if config.get("evaluate", {}).get("nms"):
+            from dpft_amd.evaluation.nms import RotatedNMS
+            self.nms = RotatedNMS.from_config(config)
         opt = dict(train["optimizer"])
         name = opt.pop("name")
         self.world = dist.get_world_size() if dist.is_initialized() else 1
@@ -634,6 +640,8 @@ class DataParallelTrainer:
             data = self._dict_to(data)
             output = self.model(data)
             loss, losses = self.loss_fn(output, labels)
+            if self.nms is not None and (self.eval_fn is not None or self.dataset_ap is not None):
+                output = self.nms.suppress(output)
             metrics = self.eval_fn(output, labels) if self.eval_fn is not None else {}
             if self.dataset_ap is not None:      # frame = rank * 2^24 + local index: only uniqueness and a fixed order matter
                 self.dataset_ap.update(output, labels, (self.rank << 24) + seen)

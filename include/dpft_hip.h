@@ -909,6 +909,27 @@ int dpft_dataset_ap_finalize_f64(const void* records_sorted, int64_t n_records, 
                                  double* npos, double* tp_total, dpft_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Rotated-box NMS between the model and its consumers (dpft_amd/evaluation/nms.py states the definition; the reference
+ * has no such step).  Three launches on `stream`, no read-back, no floating-point atomics: the same input gives the
+ * same bits.  Per sample: candidates = queries with argmax class c != 0 (first maximum, NaN = maximum) and a non-NaN
+ * score s = cls[n, c]; s >= min_score in fp32 (-INFINITY = no filter); order (score desc, query asc), -0 as +0; a
+ * candidate is suppressed by the first earlier KEPT candidate (of its class unless class_agnostic) whose fp64 IoU
+ * (kind 0 bev, 1 3d; the geometry of dpft_dataset_ap_update_f32) is strictly greater than `iou` (inside (0, 1)); kept
+ * candidates beyond the first max_det (>= 1; INT32_MAX = no limit) are dropped.
+ * status (B,N) int32: -1 kept, -2 no candidate (untouched), -3 below min_score, -4 beyond max_det, otherwise the query
+ * index of the suppressor.  order (B,N): kept queries in score order, padded with -1.  counts (B).  cls_out (B,N,C):
+ * the bits of cls, except [n, 0] = the row's winning score in every row of status >= 0, -3 or -4 (index 0 becomes the
+ * first maximum: the query reads as background downstream).  cls_out must not alias cls.
+ * `iou` points to ONE double on the HOST (the convention of iou_thrs above).
+ * scratch: dpft_nms_scratch_bytes(B, N) bytes, 16-byte aligned.  N <= 1024, 2 <= C <= 16; B == 0 or N == 0 do nothing.
+ * ---------------------------------------------------------------------------------------- */
+int64_t dpft_nms_scratch_bytes(int32_t B, int32_t N);      /* -1 + dpft_last_error() when out of range */
+int dpft_nms_f32(const float* cls, const float* center, const float* size, const float* angle, const double* iou,
+                 int32_t kind, int32_t class_agnostic, float min_score, int32_t max_det, void* scratch,
+                 int32_t* status, int32_t* order, int32_t* counts, float* cls_out, int32_t B, int32_t N, int32_t C,
+                 dpft_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * K-Radar export selection: KRadarExporter._construct_objects
  * (src/dprt/evaluation/exporters/kradar.py:231-294) for all B samples and T <= 8 confidence thresholds at once.
  * cls (B,N,C) raw scores, center (B,N,3), size (B,N,3), angle (B,N,2)=[sin,cos]; conf_thrs is a HOST array of T
