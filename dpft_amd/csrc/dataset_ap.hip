@@ -12,6 +12,12 @@
 // finalize, once per epoch: one workgroup per (class, combination) scans that class's ordered records (block prefix sum of the TP
 //               bits) into R recall bins (64-bit integer max of the precision's bit pattern), suffix maximum, AP.
 // The clip (box_iou.h, shared with nms.hip) takes (sin, cos) directly -- no atan2.
+//
+// Scene-description groups (optional, the *_groups entries): the match pass's workgroup also writes one row of a frame store
+// (frame, group bitmask from the frame's [road, time, weather] description, npos per class) at a host-known position -- no atomic;
+// the grouped finalize sums the frame rows per group (integers) and scans one workgroup per (group, class, combination) with two
+// block prefix sums per trip, membership and member-and-TP: the rank inside the group is the membership prefix.  Bin rule, suffix
+// maximum and summation order are ap_finalize_kernel's, so a group's table has the bits of an ungrouped run over its frames.
 #include "common.h"
 #include "box_iou.h"
 
@@ -42,6 +48,45 @@ struct ApArgs {
     int B, N, Mmax, C, K;
 };
 
+constexpr int kApMaxGroupB = 64, kApMaxAxes = 3, kApMaxAxisValues = 16, kApMaxGroups = 32, kApFrameRow = 2 + kApMaxC;
+// description storage of a frame: a device pointer to >= 3 elements of one of four types, or three doubles by value
+constexpr int kApDescF32 = 0, kApDescF64 = 1, kApDescI32 = 2, kApDescI64 = 3, kApDescHost = 4;
+
+struct ApGroupArgs {
+    const void* desc[kApMaxGroupB];                // per sample: the description on the device (types 0..3)
+    double host[kApMaxGroupB * 3];                 // per sample: the description by value (type 4)
+    unsigned char type[kApMaxGroupB];
+    int32_t* frames;                               // (frame capacity, kApFrameRow): frame, group mask, npos[0..15]
+    long long frame_base;                          // rows written by earlier updates
+    int n_axes;
+    int col[kApMaxAxes], count[kApMaxAxes];        // description column and number of values of every selected axis
+    int value[kApMaxAxes][kApMaxAxisValues];       // group 1 + (values of earlier axes) + i holds the frames with value[s][i]
+};
+
+// bit 0 = "all"; a non-finite value or one outside the axis's values sets no bit of that axis
+__device__ __forceinline__ unsigned ap_group_mask(const ApGroupArgs& g, int b) {
+    const int t = g.type[b];
+    const void* p = g.desc[b];
+    unsigned mask = 1u;
+    int bit = 1;
+    for (int s = 0; s < g.n_axes; ++s) {
+        const int col = g.col[s];
+        double v;
+        if (t == kApDescHost) v = g.host[b * 3 + col];
+        else if (t == kApDescF32) v = (double)((const float*)p)[col];
+        else if (t == kApDescF64) v = ((const double*)p)[col];
+        else if (t == kApDescI32) v = (double)((const int32_t*)p)[col];
+        else v = (double)((const long long*)p)[col];
+        if (fabs(v) <= 1.7976931348623157e308) {                        // (false for a NaN)
+            v = trunc(v);                                               // int(): towards zero, as the exporter reads it
+            for (int i = 0; i < g.count[s]; ++i)
+                if (v == (double)g.value[s][i]) mask |= 1u << (bit + i);
+        }
+        bit += g.count[s];
+    }
+    return mask;
+}
+
 __device__ __forceinline__ bool ap_in_roi(const ApArgs& a, const float* c) {
     if (!a.has_roi) return true;
     return (a.roi[0] < c[0]) && (c[0] < a.roi[1]) && (a.roi[2] < c[1]) && (c[1] < a.roi[3]) && (a.roi[4] < c[2]) && (c[2] < a.roi[5]);
@@ -65,7 +110,8 @@ __global__ __launch_bounds__(128) void ap_pair_kernel(ApArgs a) {
     a.pair[idx * 2 + 1] = d3;
 }
 
-__global__ __launch_bounds__(256) void ap_match_kernel(ApArgs a) {
+// `g` is a compile-time null in ap_match_kernel: the frame row below exists in ap_match_groups_kernel only
+__device__ __forceinline__ void ap_match_body(const ApArgs& a, const ApGroupArgs* g) {
     __shared__ unsigned long long key[kApMaxN];      // (score descending, query ascending) as one ascending integer
     __shared__ float score[kApMaxN];
     __shared__ unsigned tp[kApMaxN];                 // per sorted detection: bit k = TP of combination k
@@ -172,7 +218,15 @@ __global__ __launch_bounds__(256) void ap_match_kernel(ApArgs a) {
         const int q = (int)(unsigned)key[i];
         a.records[pos] = make_int4((int)__float_as_uint(score[q]), a.first_frame + b, q | ((int)label[q] << 16), (int)tp[i]);
     }
+    if (g && tid < kApFrameRow) {                                       // (the host sized the frame store: frame_base + B rows fit)
+        int32_t* row = g->frames + (g->frame_base + b) * kApFrameRow;
+        row[tid] = tid == 0 ? a.first_frame + b : tid == 1 ? (int32_t)ap_group_mask(*g, b) : npos[tid - 2];
+    }
 }
+
+__global__ __launch_bounds__(256) void ap_match_kernel(ApArgs a) { ap_match_body(a, nullptr); }
+
+__global__ __launch_bounds__(256) void ap_match_groups_kernel(ApArgs a, ApGroupArgs g) { ap_match_body(a, &g); }
 
 struct ApFinalArgs {
     const int4* rec;                       // ordered by (class, score desc, frame, query)
@@ -229,6 +283,105 @@ __global__ __launch_bounds__(256) void ap_finalize_kernel(ApFinalArgs a) {
     }
 }
 
+struct ApGroupFinalArgs {
+    const int4* rec;                       // ordered by (class, score desc, frame, query)
+    const unsigned* rec_groups;            // (n): group mask of every record's frame, in the same order
+    const long long* class_start;          // (C + 1)
+    const int32_t* frames;                 // (F, kApFrameRow)
+    double *ap, *npos, *tp_total, *nframes, *bad;      // (G,C-1,K) (G,C-1) (G,C-1,K) (G) (1)
+    long long n, F;
+    unsigned axis_mask[kApMaxAxes];        // the bits of every selected axis
+    int n_axes, G, C, K, R;
+};
+
+// blocks 0..G-1: frames and ground truth of group g (integer sums: exact in fp64); block G: frames without a group on some axis
+__global__ __launch_bounds__(256) void ap_group_frames_kernel(ApGroupFinalArgs a) {
+    __shared__ unsigned long long acc[kApMaxC + 1];
+    const int g = blockIdx.x, tid = threadIdx.x;
+    if (tid <= kApMaxC) acc[tid] = 0ull;
+    __syncthreads();
+    if (g == a.G) {
+        unsigned long long bad = 0;
+        for (long long f = tid; f < a.F; f += 256) {
+            const unsigned m = (unsigned)a.frames[f * kApFrameRow + 1];
+            bool miss = false;
+            for (int s = 0; s < a.n_axes; ++s) miss |= (m & a.axis_mask[s]) == 0u;
+            bad += miss;
+        }
+        if (bad) atomicAdd(&acc[0], bad);
+        __syncthreads();
+        if (tid == 0) a.bad[0] = (double)acc[0];
+        return;
+    }
+    unsigned long long cnt = 0, np[kApMaxC];
+#pragma unroll
+    for (int c = 0; c < kApMaxC; ++c) np[c] = 0;
+    for (long long f = tid; f < a.F; f += 256) {
+        const int32_t* row = a.frames + f * kApFrameRow;
+        if (!(((unsigned)row[1] >> g) & 1u)) continue;
+        ++cnt;
+#pragma unroll
+        for (int c = 1; c < kApMaxC; ++c) np[c] += (unsigned long long)(unsigned)row[2 + c];
+    }
+    if (cnt) atomicAdd(&acc[0], cnt);
+#pragma unroll
+    for (int c = 1; c < kApMaxC; ++c)
+        if (np[c]) atomicAdd(&acc[1 + c], np[c]);
+    __syncthreads();
+    if (tid == 0) a.nframes[g] = (double)acc[0];
+    if (tid >= 1 && tid < a.C) a.npos[g * (a.C - 1) + tid - 1] = (double)acc[1 + tid];
+}
+
+// ap_finalize_kernel restricted to the records of group g: rank and TP count are prefix sums over the members
+__global__ __launch_bounds__(256) void ap_finalize_groups_kernel(ApGroupFinalArgs a) {
+    __shared__ unsigned long long bins[kApMaxR + 1];
+    __shared__ int wmem[4], wtp[4];
+    const int k = blockIdx.x % a.K, gc = blockIdx.x / a.K, c = 1 + gc % (a.C - 1), g = gc / (a.C - 1);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long s = min(max(a.class_start[c], 0ll), a.n), e = min(max(a.class_start[c + 1], s), a.n);
+    const long long np = (long long)a.npos[g * (a.C - 1) + c - 1];
+    for (int i = tid; i <= a.R; i += 256) bins[i] = 0ull;
+    __syncthreads();
+    long long carry = 0, rank0 = 0;
+    for (long long base = s; base < e; base += 256) {
+        const long long p = base + tid;
+        const bool mem = p < e && ((a.rec_groups[p] >> g) & 1u);
+        const bool bit = mem && ((a.rec[p].w >> k) & 1);
+        const unsigned long long balm = __ballot(mem), bal = __ballot(bit);
+        if (lane == 0) { wmem[wave] = __popcll(balm); wtp[wave] = __popcll(bal); }
+        __syncthreads();
+        int off = 0, tot = 0, offm = 0, totm = 0;
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) { off += wtp[w]; offm += wmem[w]; }
+            tot += wtp[w];
+            totm += wmem[w];
+        }
+        if (bit && np > 0) {
+            const unsigned long long upto = (2ull << lane) - 1ull;
+            const long long TP = carry + off + __popcll(bal & upto);
+            const long long rank = rank0 + offm + __popcll(balm & upto);        // members up to and including p
+            long long idx = TP * a.R / np;
+            if (idx > a.R) idx = a.R;
+            const double prec = (double)TP / (double)rank;
+            if (idx >= 1) atomicMax(&bins[idx], (unsigned long long)__double_as_longlong(prec));
+        }
+        carry += tot;
+        rank0 += totm;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double env = 0, sum = 0;
+        for (int i = a.R; i >= 1; --i) {
+            env = fmax(env, __longlong_as_double((long long)bins[i]));
+            bins[i] = (unsigned long long)__double_as_longlong(env);
+        }
+        for (int i = 1; i <= a.R; ++i) sum += __longlong_as_double((long long)bins[i]);
+        const int o = (g * (a.C - 1) + c - 1) * a.K + k;
+        a.ap[o] = np > 0 ? sum / (double)a.R : __longlong_as_double(0x7ff8000000000000ll);
+        a.tp_total[o] = (double)carry;
+    }
+}
+
 static bool ap_sizes_ok(int B, int N, int Mmax, int C) {
     return B > 0 && N > 0 && N <= kApMaxN && Mmax > 0 && Mmax <= kApMaxM && C >= 2 && C <= kApMaxC;
 }
@@ -245,12 +398,12 @@ extern "C" int64_t dpft_dataset_ap_scratch_bytes(int32_t B, int32_t N, int32_t M
     return (int64_t)B * N * Mmax * 2 * (int64_t)sizeof(double);
 }
 
-extern "C" int dpft_dataset_ap_update_f32(const float* cls, const float* center, const float* size, const float* angle,
-                                          const float* gt_box, const int32_t* gt_id, const int32_t* counts,
-                                          const double* iou_thrs, const int32_t* kinds, int32_t K, const float* roi6,
-                                          float min_score, void* scratch, void* records, int64_t capacity, int64_t reserved,
-                                          int64_t* counters, int32_t first_frame, int32_t B, int32_t N, int32_t Mmax,
-                                          int32_t C, dpft_stream_t stream) {
+// argument checks and ApArgs shared by the two update entries
+static int ap_fill_update(ApArgs& a, const float* cls, const float* center, const float* size, const float* angle,
+                          const float* gt_box, const int32_t* gt_id, const int32_t* counts, const double* iou_thrs,
+                          const int32_t* kinds, int32_t K, const float* roi6, float min_score, void* scratch, void* records,
+                          int64_t capacity, int64_t reserved, int64_t* counters, int32_t first_frame, int32_t B, int32_t N,
+                          int32_t Mmax, int32_t C) {
     DPFT_REQUIRE(cls && center && size && angle && gt_box && gt_id && counts && iou_thrs && kinds && scratch && records && counters,
                  "dataset_ap_update: null argument");
     DPFT_REQUIRE(ap_sizes_ok(B, N, Mmax, C), "dataset_ap_update: sizes out of range (N <= %d, Mmax <= %d, 2 <= C <= %d)", kApMaxN,
@@ -261,7 +414,6 @@ extern "C" int dpft_dataset_ap_update_f32(const float* cls, const float* center,
                  (long long)capacity, (long long)reserved, (long long)B * N);
     DPFT_REQUIRE(((uintptr_t)records & 15) == 0 && ((uintptr_t)scratch & 7) == 0 && ((uintptr_t)counters & 7) == 0,
                  "dataset_ap_update: records need 16-byte, scratch and counters 8-byte alignment");
-    ApArgs a;
     memset(&a, 0, sizeof(a));
     for (int k = 0; k < K; ++k) {
         DPFT_REQUIRE(iou_thrs[k] > 0.0 && iou_thrs[k] < 1.0 && (kinds[k] == 0 || kinds[k] == 1),
@@ -280,12 +432,83 @@ extern "C" int dpft_dataset_ap_update_f32(const float* cls, const float* center,
     a.pair = (double*)scratch; a.records = (int4*)records; a.counters = (unsigned long long*)counters;
     a.min_score = min_score; a.capacity = capacity; a.first_frame = first_frame;
     a.B = B; a.N = N; a.Mmax = Mmax; a.C = C; a.K = K;
+    return DPFT_OK;
+}
+
+extern "C" int dpft_dataset_ap_update_f32(const float* cls, const float* center, const float* size, const float* angle,
+                                          const float* gt_box, const int32_t* gt_id, const int32_t* counts,
+                                          const double* iou_thrs, const int32_t* kinds, int32_t K, const float* roi6,
+                                          float min_score, void* scratch, void* records, int64_t capacity, int64_t reserved,
+                                          int64_t* counters, int32_t first_frame, int32_t B, int32_t N, int32_t Mmax,
+                                          int32_t C, dpft_stream_t stream) {
+    ApArgs a;
+    int rc = ap_fill_update(a, cls, center, size, angle, gt_box, gt_id, counts, iou_thrs, kinds, K, roi6, min_score, scratch, records,
+                            capacity, reserved, counters, first_frame, B, N, Mmax, C);
+    if (rc) return rc;
     const int64_t total = (int64_t)B * N * Mmax;
     hipLaunchKernelGGL(ap_pair_kernel, dim3(cdiv(total, 128)), dim3(128), 0, (hipStream_t)stream, a);
-    int rc = check_launch("dataset_ap_update pairs");
+    rc = check_launch("dataset_ap_update pairs");
     if (rc) return rc;
     hipLaunchKernelGGL(ap_match_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
     return check_launch("dataset_ap_update");
+}
+
+extern "C" int dpft_dataset_ap_update_groups_f32(const float* cls, const float* center, const float* size, const float* angle,
+                                                 const float* gt_box, const int32_t* gt_id, const int32_t* counts,
+                                                 const double* iou_thrs, const int32_t* kinds, int32_t K, const float* roi6,
+                                                 float min_score, void* scratch, void* records, int64_t capacity,
+                                                 int64_t reserved, int64_t* counters, int32_t first_frame, int32_t B, int32_t N,
+                                                 int32_t Mmax, int32_t C, const void* const* desc_ptrs,
+                                                 const int32_t* desc_types, const double* desc_host, const int32_t* axis_cols,
+                                                 const int32_t* axis_counts, const int32_t* axis_values, int32_t n_axes,
+                                                 void* frames, int64_t frame_capacity, int64_t frames_before,
+                                                 dpft_stream_t stream) {
+    DPFT_REQUIRE(desc_ptrs && desc_types && frames, "dataset_ap_update_groups: null argument");
+    DPFT_REQUIRE(n_axes == 0 || (axis_cols && axis_counts && axis_values), "dataset_ap_update_groups: null axis tables");
+    ApArgs a;
+    int rc = ap_fill_update(a, cls, center, size, angle, gt_box, gt_id, counts, iou_thrs, kinds, K, roi6, min_score, scratch, records,
+                            capacity, reserved, counters, first_frame, B, N, Mmax, C);
+    if (rc) return rc;
+    DPFT_REQUIRE(B <= kApMaxGroupB, "dataset_ap_update_groups: at most %d frames per update, got %d", kApMaxGroupB, B);
+    DPFT_REQUIRE(n_axes >= 0 && n_axes <= kApMaxAxes, "dataset_ap_update_groups: 0..%d axes, got %d", kApMaxAxes, n_axes);
+    DPFT_REQUIRE(frames_before >= 0 && frame_capacity - frames_before >= (int64_t)B && ((uintptr_t)frames & 3) == 0,
+                 "dataset_ap_update_groups: frame store too small or unaligned (capacity %lld, %lld rows before, this batch %d)",
+                 (long long)frame_capacity, (long long)frames_before, B);
+    ApGroupArgs g;
+    memset(&g, 0, sizeof(g));
+    int groups = 1;
+    for (int s = 0; s < n_axes; ++s) {
+        DPFT_REQUIRE(axis_cols[s] >= 0 && axis_cols[s] < 3 && axis_counts[s] >= 1 && axis_counts[s] <= kApMaxAxisValues,
+                     "dataset_ap_update_groups: axis %d needs a description column 0..2 and 1..%d values", s, kApMaxAxisValues);
+        g.col[s] = axis_cols[s];
+        g.count[s] = axis_counts[s];
+        for (int i = 0; i < axis_counts[s]; ++i) g.value[s][i] = axis_values[s * kApMaxAxisValues + i];
+        groups += axis_counts[s];
+    }
+    DPFT_REQUIRE(groups <= kApMaxGroups, "dataset_ap_update_groups: %d groups, at most %d", groups, kApMaxGroups);
+    static const int desc_bytes[4] = {4, 8, 4, 8};
+    for (int b = 0; b < B; ++b) {
+        const int t = desc_types[b];
+        DPFT_REQUIRE(t >= kApDescF32 && t <= kApDescHost, "dataset_ap_update_groups: description type %d of sample %d (0..4)", t, b);
+        if (t == kApDescHost) {
+            DPFT_REQUIRE(desc_host, "dataset_ap_update_groups: sample %d has its description by value but desc_host is null", b);
+            for (int i = 0; i < 3; ++i) g.host[b * 3 + i] = desc_host[b * 3 + i];
+        } else {
+            DPFT_REQUIRE(desc_ptrs[b] && ((uintptr_t)desc_ptrs[b] & (uintptr_t)(desc_bytes[t] - 1)) == 0,
+                         "dataset_ap_update_groups: description pointer of sample %d is null or unaligned", b);
+            g.desc[b] = desc_ptrs[b];
+        }
+        g.type[b] = (unsigned char)t;
+    }
+    g.frames = (int32_t*)frames;
+    g.frame_base = frames_before;
+    g.n_axes = n_axes;
+    const int64_t total = (int64_t)B * N * Mmax;
+    hipLaunchKernelGGL(ap_pair_kernel, dim3(cdiv(total, 128)), dim3(128), 0, (hipStream_t)stream, a);
+    rc = check_launch("dataset_ap_update_groups pairs");
+    if (rc) return rc;
+    hipLaunchKernelGGL(ap_match_groups_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a, g);
+    return check_launch("dataset_ap_update_groups");
 }
 
 extern "C" int dpft_dataset_ap_finalize_f64(const void* records_sorted, int64_t n_records, const int64_t* class_start,
@@ -300,4 +523,30 @@ extern "C" int dpft_dataset_ap_finalize_f64(const void* records_sorted, int64_t 
     a.n = n_records; a.C = C; a.K = K; a.R = R;
     hipLaunchKernelGGL(ap_finalize_kernel, dim3((C - 1) * K), dim3(256), 0, (hipStream_t)stream, a);
     return check_launch("dataset_ap_finalize");
+}
+
+extern "C" int dpft_dataset_ap_finalize_groups_f64(const void* records_sorted, const uint32_t* record_groups, int64_t n_records,
+                                                   const int64_t* class_start, const void* frames, int64_t n_frames,
+                                                   const uint32_t* axis_masks, int32_t n_axes, int32_t G, int32_t C, int32_t K,
+                                                   int32_t R, double* ap, double* npos, double* tp_total, double* nframes,
+                                                   double* bad, dpft_stream_t stream) {
+    DPFT_REQUIRE(records_sorted && record_groups && class_start && frames && ap && npos && tp_total && nframes && bad,
+                 "dataset_ap_finalize_groups: null argument");
+    DPFT_REQUIRE(n_records >= 0 && n_frames >= 0 && C >= 2 && C <= kApMaxC && K >= 1 && K <= kApMaxK && R >= 2 && R <= kApMaxR,
+                 "dataset_ap_finalize_groups: sizes out of range (2 <= C <= %d, 1 <= K <= %d, 2 <= R <= %d)", kApMaxC, kApMaxK,
+                 kApMaxR);
+    DPFT_REQUIRE(G >= 1 && G <= kApMaxGroups && n_axes >= 0 && n_axes <= kApMaxAxes && (n_axes == 0 || axis_masks),
+                 "dataset_ap_finalize_groups: 1..%d groups and 0..%d axes (with their masks), got %d and %d", kApMaxGroups,
+                 kApMaxAxes, G, n_axes);
+    ApGroupFinalArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int s = 0; s < n_axes; ++s) a.axis_mask[s] = axis_masks[s];
+    a.rec = (const int4*)records_sorted; a.rec_groups = record_groups; a.class_start = (const long long*)class_start;
+    a.frames = (const int32_t*)frames; a.ap = ap; a.npos = npos; a.tp_total = tp_total; a.nframes = nframes; a.bad = bad;
+    a.n = n_records; a.F = n_frames; a.n_axes = n_axes; a.G = G; a.C = C; a.K = K; a.R = R;
+    hipLaunchKernelGGL(ap_group_frames_kernel, dim3(G + 1), dim3(256), 0, (hipStream_t)stream, a);
+    int rc = check_launch("dataset_ap_finalize_groups frames");
+    if (rc) return rc;
+    hipLaunchKernelGGL(ap_finalize_groups_kernel, dim3(G * (C - 1) * K), dim3(256), 0, (hipStream_t)stream, a);
+    return check_launch("dataset_ap_finalize_groups");
 }

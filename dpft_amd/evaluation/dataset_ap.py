@@ -23,6 +23,25 @@ are K = len(kinds) * len(iou) of them, kinds outermost.
 * Split: the records of a class ordered by (score desc, frame asc, query asc); prec(p) = TP(p) / (p + 1), rec(p) = TP(p) / npos;
   AP = (1 / R) sum_{i=1..R} max{prec(p) : rec(p) >= i / R} (0 where no p qualifies), NaN for a class with npos = 0.  mAP of a
   combination = mean over the classes with npos > 0 (NaN if there is none).
+
+Scene-description groups (``groups``; tests/dataset_ap_groups_ref.py restates them).  K-Radar's table per weather condition, time
+of day and road type, which the exporter produces as one folder tree per subset, from the same accumulation:
+
+* ``label["description"]`` is [road, time, weather], each truncated to an integer the way the exporter reads it (int()).
+* Axes are "time", "road", "weather" (the exporter's order).  ``groups: true`` = all three, a list selects axes.
+* The group list is ``all``, then one group per value of each selected axis (values ascending), named ``{axis}={name}`` with the
+  names of the exporter's mappings (the ``data.*`` overrides included): at most 1 + 2 + 9 + 7 = 19 groups.
+* A frame belongs to ``all`` and, per selected axis, to the group of its value.  A value outside the axis's mapping, or a
+  non-finite one, puts the frame in no group of that axis; it still counts in ``all``, and ``bad_description`` counts the frames
+  with such a value on at least one selected axis.
+* The table of group g is the definition above applied to the frames of g and to nothing else: detections, ground truth, npos,
+  the record order, the R-point envelope, NaN for npos = 0.  Per-frame matching does not change at all.
+
+Device side with groups: ``dpft_dataset_ap_update_groups_f32`` instead of the update entry -- the SAME two launches; the workgroup
+that owns a frame also writes one row of a frame store (frame, group bitmask, npos per class).  The descriptions add NO launch
+and no copy: device tensors travel as pointers by value, host tensors as values in the kernel arguments (only a device
+description that is neither contiguous nor fp32 / fp64 / int32 / int64 costs a conversion).  ``dpft_dataset_ap_finalize_groups_f64``
+(two launches per epoch) replaces the finalize entry; its ``all`` group has the bits of the ungrouped table.
 """
 from __future__ import annotations
 
@@ -37,33 +56,89 @@ MAX_COMBINATIONS = 8
 N_COUNTERS = 32
 CURSOR, DROPPED_NAN, OVERFLOW, NPOS = 0, 1, 2, 16    # layout of the int64 counters (include/dpft_hip.h)
 _DEFAULT = object()
+AXES = ("time", "road", "weather")                   # the exporter's order (exporters/kradar.py _serialize_description)
+_AXIS_COLUMN = {"road": 0, "time": 1, "weather": 2}  # description = [road, time, weather]
+_AXIS_MAPPING = {"time": "time_zone", "road": "road_structures", "weather": "weather_conditions"}      # the data.* keys
+FRAME_ROW = 18                                       # int32 per frame: frame, group bitmask, npos of classes 0..15
+MAX_GROUP_BATCH, MAX_AXIS_VALUES, MAX_GROUPS = 64, 16, 32
+_DESC_TYPES = {torch.float32: 0, torch.float64: 1, torch.int32: 2, torch.int64: 3}
+_DESC_HOST = 4
+
+
+def _parse_groups(groups: Any) -> List[str]:
+    """None / False -> []; True -> all axes; an axis name or a list of distinct names -> those, in the exporter's order."""
+    if groups is None or groups is False:
+        return []
+    if groups is True:
+        return list(AXES)
+    axes = [groups] if isinstance(groups, str) else groups
+    if not isinstance(axes, (list, tuple)) or not axes or not all(isinstance(a, str) for a in axes) \
+            or len(set(axes)) != len(axes) or any(a not in AXES for a in axes):
+        raise ValueError(f"dataset_ap: 'groups' must be true or a non-empty list of distinct axes out of {AXES}, got {groups!r}")
+    return [a for a in AXES if a in axes]
+
+
+def _axis_tables(axes: Sequence[str], mappings: Optional[Dict[str, Any]]) -> Dict[str, List[tuple]]:
+    """axis -> [(value, name)] by ascending value, from the exporter's mappings (``mappings``: the exporter's keyword
+    arguments road_structures / weather_conditions / time_zone as name -> value dicts, None = its defaults)."""
+    from dpft_amd.evaluation.exporters.kradar import KRadarExporter
+    mappings = mappings or {}
+    unknown = sorted(set(mappings) - set(_AXIS_MAPPING.values()))
+    if unknown:
+        raise ValueError(f"dataset_ap: 'mappings' knows {sorted(_AXIS_MAPPING.values())}, got {unknown}")
+    exporter = KRadarExporter(conf_thrs=[0.0], **{k: mappings.get(k) for k in _AXIS_MAPPING.values()})
+    tables = {}
+    for axis in axes:
+        table = getattr(exporter, "_" + _AXIS_MAPPING[axis])                      # value -> name
+        for v in table:
+            if isinstance(v, bool) or not isinstance(v, int) or not -(1 << 31) <= v < (1 << 31):
+                raise ValueError(f"dataset_ap: the values of {_AXIS_MAPPING[axis]} must be int32 integers, got {v!r}")
+        if not 1 <= len(table) <= MAX_AXIS_VALUES:
+            raise ValueError(f"dataset_ap: {_AXIS_MAPPING[axis]} must have 1..{MAX_AXIS_VALUES} distinct values, got {len(table)}")
+        tables[axis] = sorted(table.items())
+    return tables
+
+
+def _gather_rows(rows: torch.Tensor) -> torch.Tensor:
+    """All ranks' rows of a 2-D tensor, concatenated in rank order (counts all-gathered, rows padded to the maximum count)."""
+    import torch.distributed as dist
+    world = dist.get_world_size()
+    n = torch.tensor([rows.shape[0]], dtype=torch.int64, device=rows.device)
+    ns = [torch.zeros_like(n) for _ in range(world)]
+    dist.all_gather(ns, n)
+    ns = [int(v) for v in ns]
+    pad = torch.zeros((max(max(ns), 1), rows.shape[1]), dtype=rows.dtype, device=rows.device)
+    pad[:rows.shape[0]] = rows
+    parts = [torch.empty_like(pad) for _ in range(world)]
+    dist.all_gather(parts, pad)
+    return torch.cat([p[:k] for p, k in zip(parts, ns)])
 
 
 def gather_state(state: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """The collective behind ``DatasetAP.all_gather`` on a raw ``state()``: record counts all-gathered, records all-gathered
     padded to the maximum count and concatenated in rank order, counters all-reduced (the cursor becomes the total count).  The
-    tensors stay on the device they are on."""
+    frame rows of a grouped accumulator (``frames``, when the state has them) are gathered like the records.  The tensors stay
+    on the device they are on."""
     import torch.distributed as dist
-    world = dist.get_world_size()
     records, counters = state["records"], state["counters"].clone()
-    n = torch.tensor([records.shape[0]], dtype=torch.int64, device=records.device)
-    ns = [torch.zeros_like(n) for _ in range(world)]
-    dist.all_gather(ns, n)
-    ns = [int(v) for v in ns]
-    pad = torch.zeros((max(max(ns), 1), 4), dtype=torch.int32, device=records.device)
-    pad[:records.shape[0]] = records
-    parts = [torch.empty_like(pad) for _ in range(world)]
-    dist.all_gather(parts, pad)
+    out = {"records": _gather_rows(records)}
     counters[CURSOR] = records.shape[0]
     dist.all_reduce(counters, op=dist.ReduceOp.SUM)
-    return {"records": torch.cat([p[:k] for p, k in zip(parts, ns)]), "counters": counters}
+    out["counters"] = counters
+    if "frames" in state:
+        out["frames"] = _gather_rows(state["frames"])
+    return out
 
 
 class DatasetAP:
     def __init__(self, num_classes: int, iou: Sequence[float] = (0.3, 0.5, 0.7), kinds: Sequence[str] = KINDS,
-                 recall_points: int = 40, min_score: float = 0.0, roi: Any = _DEFAULT, initial_capacity: int = 1 << 16):
+                 recall_points: int = 40, min_score: float = 0.0, roi: Any = _DEFAULT, initial_capacity: int = 1 << 16,
+                 groups: Any = None, mappings: Optional[Dict[str, Any]] = None, initial_frame_capacity: int = 1 << 10):
         """``roi``: [xmin, xmax, ymin, ymax, zmin, zmax] (strict inequalities) or None for no filter; default = the exporter's
-        box.  ``initial_capacity``: records the store holds before it first doubles."""
+        box.  ``initial_capacity``: records the store holds before it first doubles.  ``groups``: None, True (all axes) or a
+        list out of "time", "road", "weather" -- one more table per scene-description subset; ``mappings``: the exporter's
+        name -> value dicts under "time_zone" / "road_structures" / "weather_conditions" (None = its defaults);
+        ``initial_frame_capacity``: frames the frame store holds before it first doubles."""
         if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 2 <= num_classes <= 16:
             raise ValueError(f"dataset_ap: num_classes must be 2..16 (background + classes), got {num_classes!r}")
         iou = [iou] if isinstance(iou, (int, float)) and not isinstance(iou, bool) else iou
@@ -98,13 +173,23 @@ class DatasetAP:
         self.iou, self.kinds = [float(t) for t in iou], list(kinds)
         self.combinations = [(k, t) for k in self.kinds for t in self.iou]
         self.initial_capacity = initial_capacity
+        if isinstance(initial_frame_capacity, bool) or not isinstance(initial_frame_capacity, int) or initial_frame_capacity < 1:
+            raise ValueError(f"dataset_ap: initial_frame_capacity must be a positive integer, got {initial_frame_capacity!r}")
+        self.initial_frame_capacity = initial_frame_capacity
+        self.axes = _parse_groups(groups)
+        self.axis_tables = _axis_tables(self.axes, mappings) if self.axes else {}
+        self.group_names = ["all"] + [f"{a}={name}" for a in self.axes for _, name in self.axis_tables[a]] if self.axes else []
+        if len(self.group_names) > MAX_GROUPS:
+            raise ValueError(f"dataset_ap: {len(self.group_names)} groups, at most {MAX_GROUPS}")
         self.reset()
 
     # ------------------------------------------------------------------------------------------------------- config
     @classmethod
     def from_config(cls, config: Dict[str, Any]) -> Optional["DatasetAP"]:
-        """``config['evaluate']['dataset_ap']``: true (defaults) or a dict of iou / kinds / recall_points / min_score / roi.
-        Absent or false -> None.  The class count comes from ``config['model']['head']['num_classes']``."""
+        """``config['evaluate']['dataset_ap']``: true (defaults) or a dict of iou / kinds / recall_points / min_score / roi /
+        groups.  Absent or false -> None.  The class count comes from ``config['model']['head']['num_classes']``; with
+        ``groups`` (true, or a list out of "time", "road", "weather") the group names come from ``config['data']`` the way the
+        exporter reads them (time_zone / road_structures / weather_conditions, absent = its defaults)."""
         spec = config.get("evaluate", {}).get("dataset_ap")
         if spec is None or spec is False:
             return None
@@ -112,13 +197,16 @@ class DatasetAP:
             spec = {}
         if not isinstance(spec, dict):
             raise ValueError(f"evaluate.dataset_ap must be true or a dict, got {spec!r}")
-        unknown = sorted(set(spec) - {"iou", "kinds", "recall_points", "min_score", "roi"})
+        unknown = sorted(set(spec) - {"iou", "kinds", "recall_points", "min_score", "roi", "groups"})
         if unknown:
-            raise ValueError(f"evaluate.dataset_ap: unknown key(s) {unknown} (iou, kinds, recall_points, min_score, roi)")
+            raise ValueError(f"evaluate.dataset_ap: unknown key(s) {unknown} (iou, kinds, recall_points, min_score, roi, groups)")
         try:
             ncls = config["model"]["head"]["num_classes"]
         except (KeyError, TypeError):
             raise ValueError("evaluate.dataset_ap needs model.head.num_classes") from None
+        if _parse_groups(spec.get("groups")):
+            data = config.get("data") or {}
+            return cls(ncls, mappings={k: data.get(k) for k in _AXIS_MAPPING.values()}, **spec)
         return cls(ncls, **spec)
 
     # -------------------------------------------------------------------------------------------------------- state
@@ -126,6 +214,48 @@ class DatasetAP:
         self._records: Optional[torch.Tensor] = None      # (capacity, 4) int32 on the device
         self._counters: Optional[torch.Tensor] = None     # (N_COUNTERS) int64 on the device
         self._bound = 0                                   # host-known upper bound of the cursor: sum of B * N so far
+        self._frames: Optional[torch.Tensor] = None       # groups only: (frame capacity, FRAME_ROW) int32 on the device
+        self._nframes = 0                                 # rows of it written so far (host-known and exact: one per frame)
+
+    def _ensure_frames(self, dev: torch.device, need: int) -> None:
+        """Room for ``need`` frame rows, by doubling like the record store."""
+        cap = self._frames.shape[0] if self._frames is not None else 0
+        if self._frames is not None and cap >= need:
+            return
+        new_cap = max(cap, self.initial_frame_capacity)
+        while new_cap < need:
+            new_cap *= 2
+        new = torch.empty((new_cap, FRAME_ROW), dtype=torch.int32, device=dev)
+        if self._frames is not None and self._nframes:
+            new[:self._nframes].copy_(self._frames[:self._nframes])
+        self._frames = new
+
+    @property
+    def frame_capacity(self) -> int:
+        return 0 if self._frames is None else int(self._frames.shape[0])
+
+    def _descriptions(self, labels: List[Dict[str, torch.Tensor]], dev: torch.device):
+        """The C arguments that carry the batch's descriptions (and the tensors that must outlive the launch): a device tensor
+        goes as a pointer, a host one as three doubles, both by value in the kernel arguments."""
+        import ctypes as C
+        B = len(labels)
+        ptrs, types, host, keep = (C.c_void_p * B)(), (C.c_int32 * B)(), (C.c_double * (3 * B))(), []
+        for b, lab in enumerate(labels):
+            d = lab.get("description") if isinstance(lab, dict) else None
+            if d is None:
+                raise ValueError(f"DatasetAP.update: groups need labels[{b}]['description'] = [road, time, weather]")
+            d = torch.as_tensor(d).detach().reshape(-1)
+            if d.numel() < 3:
+                raise ValueError(f"DatasetAP.update: labels[{b}]['description'] needs [road, time, weather], got {d.numel()} value(s)")
+            if d.is_cuda:
+                if d.device != dev or d.dtype not in _DESC_TYPES or not d.is_contiguous():
+                    d = d.to(device=dev, dtype=torch.float64).contiguous()
+                keep.append(d)
+                ptrs[b], types[b] = d.data_ptr(), _DESC_TYPES[d.dtype]
+            else:
+                types[b] = _DESC_HOST
+                host[3 * b:3 * b + 3] = [float(v) for v in d[:3].to(torch.float64).tolist()]
+        return ptrs, types, host, keep
 
     def _ensure(self, dev: torch.device, need: int) -> None:
         """Room for ``need`` records; grows by doubling from the host-known bound (never from the device cursor), with a
@@ -166,6 +296,12 @@ class DatasetAP:
         if not 0 <= int(first_frame) <= 0x7FFFFFFF - B:
             raise ValueError(f"DatasetAP.update: frame indices must fit a non-negative int32, got first_frame = {first_frame}")
         dev = cls.device
+        if self.axes and B > MAX_GROUP_BATCH:      # the descriptions travel in the kernel arguments: 64 frames per launch
+            for i in range(0, B, MAX_GROUP_BATCH):
+                j = i + MAX_GROUP_BATCH
+                self.update({"class": cls[i:j], "center": center[i:j], "size": size[i:j], "angle": angle[i:j]}, labels[i:j],
+                            int(first_frame) + i)
+            return
         counts = [int(t["gt_class"].shape[0]) for t in labels]
         gt_box, _onehot, gt_id, counts_t, Mmax = pack_targets(labels, counts, ncls, dev)
         nbytes = int(lib.dpft_dataset_ap_scratch_bytes(B, N, Mmax))
@@ -177,28 +313,54 @@ class DatasetAP:
         thr = (C.c_double * K)(*[t for _, t in self.combinations])
         kinds = (C.c_int32 * K)(*[KINDS.index(k) for k, _ in self.combinations])
         roi = (C.c_float * 6)(*self.roi) if self.roi is not None else None
-        lib.call("dpft_dataset_ap_update_f32", cls.data_ptr(), center.data_ptr(), size.data_ptr(), angle.data_ptr(),
-                 gt_box.data_ptr(), gt_id.data_ptr(), counts_t.data_ptr(), thr, kinds, K, roi, self.min_score,
-                 scratch.data_ptr(), self._records.data_ptr(), self.capacity, self._bound, self._counters.data_ptr(),
-                 int(first_frame), B, N, Mmax, ncls, stream())
+        args = (cls.data_ptr(), center.data_ptr(), size.data_ptr(), angle.data_ptr(), gt_box.data_ptr(), gt_id.data_ptr(),
+                counts_t.data_ptr(), thr, kinds, K, roi, self.min_score, scratch.data_ptr(), self._records.data_ptr(),
+                self.capacity, self._bound, self._counters.data_ptr(), int(first_frame), B, N, Mmax, ncls)
+        if not self.axes:
+            lib.call("dpft_dataset_ap_update_f32", *args, stream())
+        else:
+            ptrs, types, host, _keep = self._descriptions(labels, dev)
+            self._ensure_frames(dev, self._nframes + B)
+            n_axes = len(self.axes)
+            cols = (C.c_int32 * n_axes)(*[_AXIS_COLUMN[a] for a in self.axes])
+            cnts = (C.c_int32 * n_axes)(*[len(self.axis_tables[a]) for a in self.axes])
+            vals = (C.c_int32 * (n_axes * MAX_AXIS_VALUES))()
+            for s, a in enumerate(self.axes):
+                for i, (v, _) in enumerate(self.axis_tables[a]):
+                    vals[s * MAX_AXIS_VALUES + i] = v
+            lib.call("dpft_dataset_ap_update_groups_f32", *args, ptrs, types, host, cols, cnts, vals, n_axes,
+                     self._frames.data_ptr(), self.frame_capacity, self._nframes, stream())
+            self._nframes += B
         self._bound += B * N
 
     def state(self) -> Dict[str, torch.Tensor]:
         """The raw state: ``records`` (n, 4) int32 = score bits, frame, query | class << 16, TP bits (in arbitrary order) and
-        the int64 ``counters`` ([0] = n, [1] dropped_nan, [16 + c] npos of class c).  Reads the cursor (a sync)."""
+        the int64 ``counters`` ([0] = n, [1] dropped_nan, [16 + c] npos of class c).  Reads the cursor (a sync).  With groups
+        also ``frames`` (F, 18) int32 = frame, group bitmask, npos of classes 0..15 of every frame seen (in arbitrary order)."""
         if self._counters is None:
-            return {"records": torch.empty((0, 4), dtype=torch.int32), "counters": torch.zeros(N_COUNTERS, dtype=torch.int64)}
+            st = {"records": torch.empty((0, 4), dtype=torch.int32), "counters": torch.zeros(N_COUNTERS, dtype=torch.int64)}
+            if self.axes:
+                st["frames"] = torch.empty((0, FRAME_ROW), dtype=torch.int32)
+            return st
         counters = self._counters.clone()
         host = counters.cpu()
         if int(host[OVERFLOW]):
             raise RuntimeError(f"DatasetAP: {int(host[OVERFLOW])} records did not fit the store (capacity {self.capacity})")
-        return {"records": self._records[:int(host[CURSOR])].clone(), "counters": counters}
+        st = {"records": self._records[:int(host[CURSOR])].clone(), "counters": counters}
+        if self.axes:
+            st["frames"] = self._frames[:self._nframes].clone() if self._frames is not None else \
+                torch.empty((0, FRAME_ROW), dtype=torch.int32, device=counters.device)
+        return st
 
     def load_state(self, state: Dict[str, torch.Tensor]) -> None:
         records, counters = state["records"], state["counters"]
         if records.dim() != 2 or records.shape[1] != 4 or records.dtype != torch.int32 or counters.shape != (N_COUNTERS,) \
                 or counters.dtype != torch.int64:
             raise ValueError("DatasetAP.load_state: records must be (n, 4) int32 and counters (32) int64")
+        frames = state.get("frames") if self.axes else None
+        if self.axes and (frames is None or frames.dim() != 2 or frames.shape[1] != FRAME_ROW or frames.dtype != torch.int32
+                          or frames.is_cuda != records.is_cuda):
+            raise ValueError(f"DatasetAP.load_state: with groups the state needs 'frames' (F, {FRAME_ROW}) int32 beside the records")
         n = int(records.shape[0])
         self.reset()
         if not records.is_cuda:
@@ -210,10 +372,16 @@ class DatasetAP:
         self._records[:n].copy_(records)
         self._counters.copy_(counters)
         self._counters[CURSOR] = n
+        if frames is not None:
+            self._ensure_frames(records.device, int(frames.shape[0]))
+            self._frames[:frames.shape[0]].copy_(frames)
+            self._nframes = int(frames.shape[0])
 
     def merge(self, other: "DatasetAP") -> None:
-        """Concatenates the record stores and adds the counters (the frames of the two must not overlap)."""
-        if (other.combinations, other.num_classes, other.recall_points) != (self.combinations, self.num_classes, self.recall_points):
+        """Concatenates the record stores (with groups also the frame stores) and adds the counters (the frames of the two must
+        not overlap)."""
+        if (other.combinations, other.num_classes, other.recall_points, other.group_names, other.axis_tables) != \
+                (self.combinations, self.num_classes, self.recall_points, self.group_names, self.axis_tables):
             raise ValueError("DatasetAP.merge: the two accumulators differ in their parameters")
         a, b = self.state(), other.state()
         if not b["records"].is_cuda:
@@ -221,19 +389,23 @@ class DatasetAP:
         if not a["records"].is_cuda:
             self.load_state(b)
             return
-        self.load_state({"records": torch.cat((a["records"], b["records"].to(a["records"].device))),
-                         "counters": a["counters"] + b["counters"].to(a["counters"].device)})
+        st = {"records": torch.cat((a["records"], b["records"].to(a["records"].device))),
+              "counters": a["counters"] + b["counters"].to(a["counters"].device)}
+        if self.axes:
+            st["frames"] = torch.cat((a["frames"], b["frames"].to(a["frames"].device)))
+        self.load_state(st)
 
     def all_gather(self) -> None:
         """Under ``torch.distributed`` with more than one rank: every rank ends up with all ranks' records and the summed
-        counters (``gather_state``), so every rank computes the same table.  A no-op otherwise."""
+        counters (``gather_state``; with groups also all ranks' frame rows), so every rank computes the same table.  A no-op
+        otherwise."""
         import torch.distributed as dist
         if not (dist.is_initialized() and dist.get_world_size() > 1):
             return
         st = self.state()
         if not st["records"].is_cuda:      # a rank that saw no batch still takes part in the collectives
             dev = torch.device("cuda", torch.cuda.current_device())
-            st = {"records": st["records"].to(dev), "counters": st["counters"].to(dev)}
+            st = {k: v.to(dev) for k, v in st.items()}
         self.load_state(gather_state(st))
 
     # ------------------------------------------------------------------------------------------------------- result
@@ -258,10 +430,18 @@ class DatasetAP:
     @torch.no_grad()
     def compute(self) -> Dict[str, Any]:
         """Python floats under ``AP_{kind}@{iou}/{c}``, ``mAP_{kind}@{iou}``, ``npos/{c}``, ``dropped_nan``; the fp64 tensors
-        ``ap`` (C-1, K), ``npos`` (C-1) and ``tp`` (C-1, K: TP totals) on the host."""
+        ``ap`` (C-1, K), ``npos`` (C-1) and ``tp`` (C-1, K: TP totals) on the host.  With groups also, per group other than
+        ``all``, ``AP_{kind}@{iou}/{c}/{axis}={name}``, ``mAP_{kind}@{iou}/{axis}={name}``, ``npos/{c}/{axis}={name}`` and
+        ``nframes/{axis}={name}``, the count ``bad_description``, the fp64 tensors ``group_ap`` (G, C-1, K), ``group_tp``
+        (G, C-1, K), ``group_npos`` (G, C-1), ``group_nframes`` (G) and the list ``group_names`` (``all`` first); the keys
+        without a group are then the ``all`` group's."""
         from dpft_amd.hip.lib import lib, stream
         Cn, K = self.num_classes, len(self.combinations)
-        if self._counters is None:
+        groups = None
+        if self.axes:
+            groups = self._compute_groups()
+            ap, tp, npos, dropped = groups["group_ap"][0], groups["group_tp"][0], groups["group_npos"][0], groups.pop("dropped")
+        elif self._counters is None:
             ap = torch.full((Cn - 1, K), float("nan"), dtype=torch.float64)
             npos, tp, dropped = torch.zeros(Cn - 1, dtype=torch.float64), torch.zeros((Cn - 1, K), dtype=torch.float64), 0
         else:
@@ -292,8 +472,68 @@ class DatasetAP:
             res[f"npos/{c}"] = float(npos[c - 1])
         res["dropped_nan"] = float(dropped)
         res["ap"], res["npos"], res["tp"] = ap, npos, tp
+        if groups is not None:
+            all_ap, all_npos, all_nframes = (groups[k].tolist() for k in ("group_ap", "group_npos", "group_nframes"))
+            for g, gname in enumerate(self.group_names[1:], 1):      # (plain lists: ~800 reads of a host tensor cost milliseconds)
+                gap, gnpos = all_ap[g], all_npos[g]
+                for k, (kind, thr) in enumerate(self.combinations):
+                    name = self.key(kind, thr)
+                    vals = [gap[c][k] for c in range(Cn - 1) if gnpos[c] > 0]
+                    for c in range(1, Cn):
+                        res[f"AP_{name}/{c}/{gname}"] = gap[c - 1][k]
+                    res[f"mAP_{name}/{gname}"] = sum(vals) / len(vals) if vals else float("nan")
+                for c in range(1, Cn):
+                    res[f"npos/{c}/{gname}"] = gnpos[c - 1]
+                res[f"nframes/{gname}"] = all_nframes[g]
+            res["bad_description"] = float(groups.pop("bad"))
+            res.update(groups)
+            res["group_names"] = list(self.group_names)
         return res
+
+    def _compute_groups(self) -> Dict[str, Any]:
+        """The grouped finalize: the records sorted as always, every record's group bitmask looked up in the frame store by its
+        frame index (one more sort and a searchsorted), then ``dpft_dataset_ap_finalize_groups_f64`` and one read-back."""
+        import ctypes as C
+        from dpft_amd.hip.lib import lib, stream
+        Cn, K, G = self.num_classes, len(self.combinations), len(self.group_names)
+        sizes = (G * (Cn - 1) * K, G * (Cn - 1) * K, G * (Cn - 1), G, 1)          # ap, tp, npos, nframes, bad
+        if self._counters is None:
+            host = torch.cat([torch.full((sizes[0],), float("nan"), dtype=torch.float64),
+                              torch.zeros(sum(sizes[1:]), dtype=torch.float64)])
+            dropped = 0
+        else:
+            st = self.state()
+            dev = st["counters"].device
+            rec = self.sort_records(st["records"])
+            n, F = int(rec.shape[0]), int(st["frames"].shape[0])
+            cls_of = (rec[:, 2] >> 16) & 0xFF
+            start = torch.searchsorted(cls_of.contiguous(), torch.arange(Cn + 1, dtype=cls_of.dtype, device=dev)).to(torch.int64)
+            if n and F:
+                order = torch.sort(st["frames"][:, 0]).indices
+                frame_of, mask_of = st["frames"][order, 0].contiguous(), st["frames"][order, 1]
+                of = rec[:, 1].contiguous()
+                idx = torch.searchsorted(frame_of, of).clamp_(max=F - 1)
+                rec_groups = torch.where(frame_of[idx] == of, mask_of[idx], torch.zeros_like(of)).contiguous()
+            else:
+                rec_groups = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+            if n == 0:
+                rec = torch.zeros((1, 4), dtype=torch.int32, device=dev)
+            frames = st["frames"] if F else torch.zeros((1, FRAME_ROW), dtype=torch.int32, device=dev)
+            masks, bit = (C.c_uint32 * len(self.axes))(), 1
+            for s, a in enumerate(self.axes):
+                masks[s] = ((1 << len(self.axis_tables[a])) - 1) << bit
+                bit += len(self.axis_tables[a])
+            out = torch.empty(sum(sizes), dtype=torch.float64, device=dev)
+            o = [sum(sizes[:i]) for i in range(5)]
+            lib.call("dpft_dataset_ap_finalize_groups_f64", rec.data_ptr(), rec_groups.data_ptr(), n, start.data_ptr(),
+                     frames.data_ptr(), F, masks, len(self.axes), G, Cn, K, self.recall_points, out[o[0]:].data_ptr(),
+                     out[o[2]:].data_ptr(), out[o[1]:].data_ptr(), out[o[3]:].data_ptr(), out[o[4]:].data_ptr(), stream())
+            host = out.cpu()
+            dropped = int(st["counters"][DROPPED_NAN])
+        ap, tp, npos, nframes, bad = torch.split(host, sizes)
+        return {"group_ap": ap.reshape(G, Cn - 1, K), "group_tp": tp.reshape(G, Cn - 1, K), "group_npos": npos.reshape(G, Cn - 1),
+                "group_nframes": nframes.clone(), "bad": int(bad[0]), "dropped": dropped}
 
     def scalars(self) -> Dict[str, float]:
         """``compute()`` without the tensors: what the evaluation loops return and log."""
-        return {k: v for k, v in self.compute().items() if not isinstance(v, torch.Tensor)}
+        return {k: v for k, v in self.compute().items() if isinstance(v, float)}

@@ -111,7 +111,8 @@ class DataParallelEvaluator:
         (default: the loader's ``sampler.start``, else 0) -- the exporter numbers its files from it.  ``rank`` / ``world``
         default to the process group's (tests pass them to play several ranks in one process).  Returns the metric means over
         ALL ranks' steps; with a ``dataset_ap`` also its split-level scalars (``AP_*``, ``mAP_*``, ``npos/*``, ``dropped_nan``),
-        which are no step means: they are computed once from all ranks' records."""
+        which are no step means: they are computed once from all ranks' records (with its ``groups`` also one such table per
+        scene-description subset: ``.../{axis}={name}``, ``nframes/*``, ``bad_description``)."""
         rank = self.rank if rank is None else rank
         world = self.world if world is None else world
         if shard_start is None:

@@ -909,6 +909,40 @@ int dpft_dataset_ap_finalize_f64(const void* records_sorted, int64_t n_records, 
                                  double* npos, double* tp_total, dpft_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Split-level AP per scene-description group (evaluate.dataset_ap.groups; dpft_amd/evaluation/dataset_ap.py).  Group 0
+ * is "all"; every selected axis s < n_axes (<= 3) adds axis_counts[s] (1..16) groups, one per entry of
+ * axis_values[s * 16 + i], in this order; at most 32 groups.  axis_cols[s] is the axis's column of the frame's
+ * description [road, time, weather].  A description value is truncated towards zero; a non-finite one, or one equal to
+ * no entry, leaves the frame without a group on that axis.
+ * update_groups: dpft_dataset_ap_update_f32 (same two launches, same records and counters) whose match pass also writes
+ *   row frames_before + b of the frame store `frames` (frame_capacity rows of 18 int32: first_frame + b, group bitmask,
+ *   ground-truth count of classes 0..15) -- no atomic; frame_capacity - frames_before >= B and B <= 64 are required.
+ *   The descriptions travel by value: desc_types[b] (HOST array) = 0 fp32, 1 fp64, 2 int32, 3 int64 with desc_ptrs[b]
+ *   (HOST array of DEVICE pointers to >= 3 elements, aligned to the element), or 4 = the three doubles desc_host[3 * b ..]
+ *   (HOST).  axis_cols, axis_counts and axis_values (n_axes x 16 int32) are HOST arrays.
+ * finalize_groups (two launches): record_groups (n_records uint32, device) = the group bitmask of every sorted record's
+ *   frame; frames = the n_frames rows of the frame store in any order; axis_masks (HOST, n_axes) = the bits of every
+ *   axis.  First nframes (G), npos (G,C-1) and bad[0] (frames without a group on some axis) as integer sums over the
+ *   frame rows, then one workgroup per (group, class, combination): dpft_dataset_ap_finalize_f64 applied to the member
+ *   records alone (rank = members so far), ap (G,C-1,K) and tp_total (G,C-1,K); all fp64, the bits of an ungrouped run
+ *   over the group's frames.
+ * ---------------------------------------------------------------------------------------- */
+int dpft_dataset_ap_update_groups_f32(const float* cls, const float* center, const float* size, const float* angle,
+                                      const float* gt_box, const int32_t* gt_id, const int32_t* counts,
+                                      const double* iou_thrs, const int32_t* kinds, int32_t K, const float* roi6,
+                                      float min_score, void* scratch, void* records, int64_t capacity, int64_t reserved,
+                                      int64_t* counters, int32_t first_frame, int32_t B, int32_t N, int32_t Mmax,
+                                      int32_t C, const void* const* desc_ptrs, const int32_t* desc_types,
+                                      const double* desc_host, const int32_t* axis_cols, const int32_t* axis_counts,
+                                      const int32_t* axis_values, int32_t n_axes, void* frames, int64_t frame_capacity,
+                                      int64_t frames_before, dpft_stream_t stream);
+int dpft_dataset_ap_finalize_groups_f64(const void* records_sorted, const uint32_t* record_groups, int64_t n_records,
+                                        const int64_t* class_start, const void* frames, int64_t n_frames,
+                                        const uint32_t* axis_masks, int32_t n_axes, int32_t G, int32_t C, int32_t K,
+                                        int32_t R, double* ap, double* npos, double* tp_total, double* nframes,
+                                        double* bad, dpft_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Rotated-box NMS between the model and its consumers (dpft_amd/evaluation/nms.py states the definition; the reference
  * has no such step).  Three launches on `stream`, no read-back, no floating-point atomics: the same input gives the
  * same bits.  Per sample: candidates = queries with argmax class c != 0 (first maximum, NaN = maximum) and a non-NaN

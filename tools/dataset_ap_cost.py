@@ -6,8 +6,15 @@
 2. ``DatasetAP.compute()`` on about 2 * 10^5 records (wall clock: it ends with a read-back), split into its sort (torch) and the
    finalize launch.
 
-Prints JSON lines and writes them to ``--out`` (default profiles/dataset_ap.txt).
-Usage: python tools/dataset_ap_cost.py [--reps 200] [--records 200000] [--out profiles/dataset_ap.txt]"""
+With ``--groups`` the groups leg instead (evaluate.dataset_ap.groups, all three axes = 19 groups), every figure beside the
+ungrouped one of the same process:
+
+3. ``DatasetAP.update`` with and without groups on the same tensors (descriptions on the device, and on the host).
+4. ``DatasetAP.compute()`` on about 2 * 10^5 records with 19 groups beside the ungrouped ``compute()`` on the same records, and
+   the two finalize entries alone between device events.
+
+Prints JSON lines and writes them to ``--out`` (default profiles/dataset_ap.txt, with ``--groups`` profiles/dataset_ap_groups.txt).
+Usage: python tools/dataset_ap_cost.py [--groups] [--reps 200] [--records 200000] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -25,8 +32,11 @@ def main():
     p = argparse.ArgumentParser()
     p.add_argument("--reps", type=int, default=200)
     p.add_argument("--records", type=int, default=200000)
-    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "dataset_ap.txt"))
+    p.add_argument("--groups", action="store_true", help="the groups leg (3., 4.) instead of 1. and 2.")
+    p.add_argument("--out", default=None)
     args = p.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "dataset_ap_groups.txt" if args.groups else "dataset_ap.txt")
     import numpy as np
     import torch
     import dataset_ap_ref as R                                  # the tests' seeded sample builder
@@ -63,6 +73,12 @@ def main():
         torch.cuda.synchronize()
         t = sorted(a.elapsed_time(b) * 1e3 for a, b in ev)
         return {"median_us": round(statistics.median(t), 1), "min_us": round(t[0], 1), "p90_us": round(t[int(0.9 * len(t))], 1)}
+
+    if args.groups:
+        groups_leg(args, torch, DatasetAP, lib, stream, dev, out, labels, B, N, Cn, timed, emit)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
 
     frame = [0]
 
@@ -129,6 +145,82 @@ def main():
           "mAP_3d@0.5": res["mAP_3d@0.5"]})
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")
+
+
+def groups_leg(args, torch, DatasetAP, lib, stream, dev, out, labels, B, N, Cn, timed, emit):
+    """3. and 4. of the module docstring: a grouped and an ungrouped accumulator fed the same batches in the same process."""
+    def described(where, first):
+        return [dict(l, description=torch.tensor([(first + b) % 9, (first + b) % 2, (first + b) % 7], dtype=torch.float32).to(where))
+                for b, l in enumerate(labels)]
+    plain, grouped = DatasetAP(Cn, initial_capacity=1 << 22), DatasetAP(Cn, initial_capacity=1 << 22, groups=True,
+                                                                         initial_frame_capacity=1 << 16)
+    on_dev, on_host = described(dev, 0), described("cpu", 0)
+    frame = {"plain": 0, "dev": 0, "host": 0}
+
+    def update(ap, labs, key):
+        def fn():
+            ap.update(out, labs, frame[key])
+            frame[key] += B
+        return fn
+
+    plain.update(out, labels, 0)
+    n_det = int(plain.state()["counters"][0])
+    plain.reset()
+    t_plain = timed(update(plain, labels, "plain"))
+    t_dev = timed(update(grouped, on_dev, "dev"))
+    grouped.reset()
+    t_host = timed(update(grouped, on_host, "host"))
+    emit({"what": "update with and without groups, between device events", "device": torch.cuda.get_device_name(0), "B": B, "N": N,
+          "C": Cn, "K": len(plain.combinations), "groups": len(grouped.group_names), "detections_per_update": n_det, "reps": args.reps,
+          "DatasetAP.update without groups": t_plain, "DatasetAP.update with groups, descriptions on the device": t_dev,
+          "DatasetAP.update with groups, descriptions on the host": t_host})
+
+    # compute() on ~ --records records: the same batch under new frame numbers, the descriptions walking all 19 groups
+    plain.reset()
+    grouped.reset()
+    first = 0
+    while plain._bound < args.records * N // max(n_det // B, 1):
+        plain.update(out, labels, first)
+        grouped.update(out, described(dev, first), first)
+        first += B
+    torch.cuda.synchronize()
+    walls = {"plain": [], "grouped": []}
+    for _ in range(5):
+        for key, ap in (("plain", plain), ("grouped", grouped)):
+            t0 = time.perf_counter()
+            res = ap.compute()
+            walls[key].append((time.perf_counter() - t0) * 1e3)
+    assert torch.equal(res["group_ap"][0].view(torch.int64), plain.compute()["ap"].view(torch.int64))
+
+    # the finalize entries alone, on the sorted records
+    st = grouped.state()
+    rec = DatasetAP.sort_records(st["records"])
+    n, F, G, K = int(rec.shape[0]), int(st["frames"].shape[0]), len(grouped.group_names), len(plain.combinations)
+    cls_of = (rec[:, 2] >> 16) & 0xFF
+    start = torch.searchsorted(cls_of.contiguous(), torch.arange(Cn + 1, dtype=cls_of.dtype, device=dev)).to(torch.int64)
+    order = torch.sort(st["frames"][:, 0]).indices
+    frame_of, mask_of = st["frames"][order, 0].contiguous(), st["frames"][order, 1]
+    rec_groups = mask_of[torch.searchsorted(frame_of, rec[:, 1].contiguous())].contiguous()
+    buf = torch.empty(G * (Cn - 1) * (2 * K + 1) + G + 1, dtype=torch.float64, device=dev)
+    o = [0, G * (Cn - 1) * K, 2 * G * (Cn - 1) * K, 2 * G * (Cn - 1) * K + G * (Cn - 1), 2 * G * (Cn - 1) * K + G * (Cn - 1) + G]
+    masks = (C.c_uint32 * 3)(0x6, 0xFF8, 0x7F000)
+
+    def finalize_groups():
+        lib.call("dpft_dataset_ap_finalize_groups_f64", rec.data_ptr(), rec_groups.data_ptr(), n, start.data_ptr(),
+                 st["frames"].data_ptr(), F, masks, 3, G, Cn, K, 40, buf[o[0]:].data_ptr(), buf[o[2]:].data_ptr(),
+                 buf[o[1]:].data_ptr(), buf[o[3]:].data_ptr(), buf[o[4]:].data_ptr(), stream())
+
+    def finalize_plain():
+        lib.call("dpft_dataset_ap_finalize_f64", rec.data_ptr(), n, start.data_ptr(), st["counters"].data_ptr(), Cn, K, 40,
+                 buf[o[0]:].data_ptr(), buf[o[2]:].data_ptr(), buf[o[1]:].data_ptr(), stream())
+
+    emit({"what": "compute() wall clock, ms, with 19 groups beside the ungrouped compute() on the same records", "records": n,
+          "frames": F, "groups": G, "compute_ms_median without groups": round(statistics.median(walls["plain"]), 2),
+          "compute_ms_median with groups": round(statistics.median(walls["grouped"]), 2),
+          "compute_ms_min without groups": round(min(walls["plain"]), 2), "compute_ms_min with groups": round(min(walls["grouped"]), 2),
+          "dpft_dataset_ap_finalize_f64 alone": timed(finalize_plain),
+          "dpft_dataset_ap_finalize_groups_f64 alone (one workgroup per group, class, combination)": timed(finalize_groups),
+          "mAP_3d@0.5/weather=fog": res["mAP_3d@0.5/weather=fog"]})
 
 
 if __name__ == "__main__":
