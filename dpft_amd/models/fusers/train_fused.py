@@ -240,6 +240,45 @@ def _pack_views(params: List[torch.Tensor], V: int, n_levels, n_points, dev):
     return packed, views
 
 
+def _xf_weight_grads(rows: torch.Tensor, n_levels, n_points) -> list:
+    """rows (V,B*Q,XR_FLOATS) of dpft_xattn_ffn_train_bwd_f32 -> the 22 parameter gradients of every view in ``view_params``
+    order (None for the six self-attention tensors): every one a product of two column blocks of `rows`, summed over the
+    rows, in one launch."""
+    V = rows.shape[0]
+    X = _XR
+    specs, off = [], 0
+
+    def add(ca, na, cb, nb):
+        nonlocal off
+        specs.append((ca, na, cb, nb, off))
+        off += na * (1 if cb < 0 else nb)
+        return off - na * (1 if cb < 0 else nb)
+    o_col = add(0, X["QP"], -1, 1)                                            # (640) vector gradients
+    o_oa = add(X["DLIN"], X["DF"] - X["DLIN"], X["QP"], 16)                   # (480,16)
+    o_f2 = add(X["DF"], X["DPRE"] - X["DF"], X["HD"], 32)                     # (16,32)
+    o_f1 = add(X["DPRE"], X["DOUT"] - X["DPRE"], X["Y2"], 16)                 # (32,16)
+    o_op = add(X["DOUT"], X["G3"] - X["DOUT"], X["VEC"], 16)                  # (16,16)
+    o_vw = [add(X["DVEC"] + 2 * m, 2, X["SAMP"] + 16 * m, 16) for m in range(8)][0]       # (8,2,16)
+    res = _rows_outer(rows, specs, off)
+    col = res[:, o_col:o_col + X["QP"]]
+    g_oa = res[:, o_oa:o_oa + 480 * 16].view(V, 480, 16)
+    g_f2 = res[:, o_f2:o_f2 + 512].view(V, 16, 32)
+    g_f1 = res[:, o_f1:o_f1 + 512].view(V, 32, 16)
+    g_op = res[:, o_op:o_op + 256].view(V, 16, 16)
+    g_vw = res[:, o_vw:o_vw + 256].view(V, 16, 16)
+    grads = []
+    for v in range(V):
+        n_off = 8 * n_levels[v] * n_points[v] * 2
+        n_att = n_off // 2
+        grads += [None] * 6
+        grads += [g_oa[v, :n_off], col[v, :n_off], g_oa[v, n_off:n_off + n_att], col[v, n_off:n_off + n_att],
+                  g_vw[v], col[v, X["DBV"]:X["DVEC"]], g_op[v], col[v, X["DOUT"]:X["G3"]],
+                  col[v, X["G2"]:X["B2"]], col[v, X["B2"]:X["DBV"]],
+                  g_f1[v], col[v, X["DPRE"]:X["DOUT"]], g_f2[v], col[v, X["DF"]:X["DPRE"]],
+                  col[v, X["G3"]:X["B3"]], col[v, X["B3"]:X["G2"]]]
+    return grads
+
+
 class XattnFfnBlocksFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, states, seed, salt: int, p_drop: float, n_points, y1, pos_dep, refs, pos, hub, *rest):
@@ -293,37 +332,7 @@ class XattnFfnBlocksFn(torch.autograd.Function):
                  V, C.cast(npts, C.c_void_p), y1.data_ptr(), pos.data_ptr(), refs.data_ptr(), p_drop, seed.data_ptr(),
                  salt, saved.data_ptr(), dy3.data_ptr(), dy1.data_ptr(), dqp.data_ptr(), dref.data_ptr(), rows.data_ptr(),
                  scratch.data_ptr() if scratch is not None else None, B, Q, stream())
-        X = _XR
-        # every weight gradient = a product of two column blocks of `rows`, summed over the rows: one launch
-        specs, off = [], 0
-        def add(ca, na, cb, nb):
-            nonlocal off
-            specs.append((ca, na, cb, nb, off))
-            off += na * (1 if cb < 0 else nb)
-            return off - na * (1 if cb < 0 else nb)
-        o_col = add(0, X["QP"], -1, 1)                                            # (640) vector gradients
-        o_oa = add(X["DLIN"], X["DF"] - X["DLIN"], X["QP"], 16)                   # (480,16)
-        o_f2 = add(X["DF"], X["DPRE"] - X["DF"], X["HD"], 32)                     # (16,32)
-        o_f1 = add(X["DPRE"], X["DOUT"] - X["DPRE"], X["Y2"], 16)                 # (32,16)
-        o_op = add(X["DOUT"], X["G3"] - X["DOUT"], X["VEC"], 16)                  # (16,16)
-        o_vw = [add(X["DVEC"] + 2 * m, 2, X["SAMP"] + 16 * m, 16) for m in range(8)][0]       # (8,2,16)
-        res = _rows_outer(rows, specs, off)
-        col = res[:, o_col:o_col + X["QP"]]
-        g_oa = res[:, o_oa:o_oa + 480 * 16].view(V, 480, 16)
-        g_f2 = res[:, o_f2:o_f2 + 512].view(V, 16, 32)
-        g_f1 = res[:, o_f1:o_f1 + 512].view(V, 32, 16)
-        g_op = res[:, o_op:o_op + 256].view(V, 16, 16)
-        g_vw = res[:, o_vw:o_vw + 256].view(V, 16, 16)
-        grads = []
-        for v in range(V):
-            n_off = 8 * n_levels[v] * n_points[v] * 2
-            n_att = n_off // 2
-            grads += [None] * 6
-            grads += [g_oa[v, :n_off], col[v, :n_off], g_oa[v, n_off:n_off + n_att], col[v, n_off:n_off + n_att],
-                      g_vw[v], col[v, X["DBV"]:X["DVEC"]], g_op[v], col[v, X["DOUT"]:X["G3"]],
-                      col[v, X["G2"]:X["B2"]], col[v, X["B2"]:X["DBV"]],
-                      g_f1[v], col[v, X["DPRE"]:X["DOUT"]], g_f2[v], col[v, X["DF"]:X["DPRE"]],
-                      col[v, X["G3"]:X["B3"]], col[v, X["B3"]:X["G2"]]]
+        grads = _xf_weight_grads(rows, n_levels, n_points)
         gtok = [None] * V                       # tokens carry ordering only (_PyramidHub ignores their gradient)
         if ctx.hub is not None:
             ctx.hub.parts.append(dqp)
