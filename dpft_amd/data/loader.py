@@ -7,6 +7,7 @@
 * ``PrefetchLoader`` -- wraps any iterable of (inputs, targets) host batches: a worker thread stages them in pinned
   memory, uploads them on its own HIP stream, runs the ``GpuPreprocessor`` there and hands over (batch, labels) with an
   event the consumer's stream waits on, so upload + preprocessing of batch i+1 overlap the training step of batch i.
+  A preprocessor that augments (``train.augment``, dpft_amd/data/augment.py) is handed the labels too and returns both.
 """
 from __future__ import annotations
 
@@ -233,6 +234,9 @@ class PrefetchLoader:
             if self.slots is not None:
                 reuse = max(1, self.slots.per_worker - 2) * self.slots.n_workers
             it, i = iter(self.source), -1
+            augments = getattr(self.preprocessor, "augments", False)
+            if augments:                                        # the draws of an epoch follow the sampler's epoch
+                self.preprocessor.set_epoch(getattr(self.sampler, "epoch", 0))
             while True:
                 i += 1
                 if reuse is not None:
@@ -259,7 +263,9 @@ class PrefetchLoader:
                 with torch.cuda.stream(up):
                     batch = _to_device(host[0], self.device)
                     labels = _to_device(host[1], self.device)
-                    if self.preprocessor is not None:
+                    if augments:                                # the flip moves the labels with the frames
+                        batch, labels = self.preprocessor(batch, labels)
+                    elif self.preprocessor is not None:
                         batch = self.preprocessor(batch)
                     ev = torch.cuda.Event()
                     ev.record(up)
@@ -331,6 +337,9 @@ def load_listed_eval(dataset: Dataset, config: Dict[str, Any], device="cpu", ran
     scored and exported exactly once and keeps the file index it has in a one-process run.  The returned loader exposes
     ``.sampler`` (``.start`` = the block's first global index, which ``DataParallelEvaluator.evaluate_one_epoch`` numbers the
     export files from)."""
+    if getattr(preprocessor, "augments", False):
+        raise ValueError("load_listed_eval: the training augmentation never runs in evaluation; build the preprocessor with "
+                         "GpuPreprocessor.from_config(config) (augment left False)")
     sampler = BlockShardedSampler(len(dataset), rank, world)
     workers = config.get("computing", {}).get("workers", 0)
     dl = DataLoader(dataset, batch_size=config["train"]["batch_size"], sampler=sampler, num_workers=workers,

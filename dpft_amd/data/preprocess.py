@@ -60,18 +60,43 @@ def scale_clip(x: torch.Tensor, in_lo: float = MIN_POWER, in_hi: float = MAX_POW
 
 
 class GpuPreprocessor:
+    """``augment``: None / False (off: the plain transforms, exactly), or a ``train.augment`` value / an
+    ``AugmentSampler`` -- the training augmentation of dpft_amd/data/augment.py.  An augmenting preprocessor is called with
+    the labels, ``pre(batch, labels) -> (batch, labels)``: the flip moves frames, radar maps, matrices and labels together."""
+
     def __init__(self, image_size: Union[int, Sequence[int], None] = 512, scale: bool = True,
                  camera_keys: Sequence[str] = ("camera_mono", "camera_stereo"),
-                 radar_keys: Sequence[str] = ("radar_bev", "radar_front")):
+                 radar_keys: Sequence[str] = ("radar_bev", "radar_front"), augment=None, seed: int = 0, rank: int = 0):
         self.image_size, self.scale = image_size, scale
         self.camera_keys, self.radar_keys = tuple(camera_keys), tuple(radar_keys)
+        self.sampler = None
+        if augment is not None and augment is not False:
+            from dpft_amd.data.augment import AugmentSampler, parse_augment
+            self.sampler = augment if isinstance(augment, AugmentSampler) else AugmentSampler(parse_augment(augment), seed, rank)
+
+    @property
+    def augments(self) -> bool:
+        return self.sampler is not None
+
+    def set_epoch(self, epoch: int) -> None:
+        if self.sampler is not None:
+            self.sampler.set_epoch(epoch)
 
     @classmethod
-    def from_config(cls, config: Dict) -> "GpuPreprocessor":
+    def from_config(cls, config: Dict, augment: bool = False, rank: int = 0) -> "GpuPreprocessor":
+        """``augment=True`` (the TRAINING loader only): take ``train.augment`` of the config, if it has the key."""
         d = config.get("data", {})
-        return cls(image_size=d.get("image_size", 512), scale=d.get("scale", True))
+        spec, seed = None, 0
+        if augment and "augment" in config.get("train", {}):
+            from dpft_amd.data.augment import check_fov_symmetric, parse_augment
+            spec = parse_augment(config["train"]["augment"])
+            check_fov_symmetric(spec, d.get("fov"))
+            seed = config.get("computing", {}).get("seed", 0)
+        return cls(image_size=d.get("image_size", 512), scale=d.get("scale", True), augment=spec, seed=seed, rank=rank)
 
-    def __call__(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    def __call__(self, batch: Dict[str, torch.Tensor], labels=None):
+        if self.sampler is not None:
+            return self._augmented(batch, labels)
         out = dict(batch)
         for k in self.radar_keys:
             if k in out and self.scale:
@@ -85,3 +110,36 @@ class GpuPreprocessor:
                     v = v.float()
                 out[k] = v
         return out
+
+    def _augmented(self, batch: Dict[str, torch.Tensor], labels, params=None):
+        """The augmented transforms: one launch per view in place of its resize / scaling launch, and the geometry launch.
+        ``params`` (a list of ``SampleParams``) overrides the sampler's draw."""
+        from dpft_amd.data import augment as A
+        if labels is None:
+            raise ValueError("GpuPreprocessor: an augmenting preprocessor needs the labels, pre(batch, labels): a flipped "
+                             "frame with unflipped labels is silent corruption")
+        views = [k for k in self.camera_keys + self.radar_keys if k in batch]
+        if not views:
+            return dict(batch), list(labels)
+        B = batch[views[0]].shape[0]
+        if len(labels) != B:
+            raise ValueError(f"GpuPreprocessor: {len(labels)} label dicts for a batch of {B}")
+        if params is None:
+            params = self.sampler.draw(B)
+        params = A.pack_samples(params)                      # once for the batch's launches
+        out = dict(batch)
+        for k in self.radar_keys:
+            if k in out:
+                out[k] = A.augment_radar(out[k], params, scale=self.scale)
+        for k in self.camera_keys:
+            if k in out:
+                v = out[k]
+                size = None if self.image_size is None else resized_output_size(v.shape[1], v.shape[2], self.image_size)
+                out[k] = A.augment_camera(v, size, params)
+        geo = [k for k in views if f"label_to_{k}_p" in out]
+        new, labels = A.augment_geometry(
+            [(out[f"label_to_{k}_t"], out[f"label_to_{k}_p"], out[f"{k}_shape"], k in self.camera_keys) for k in geo],
+            labels, params)
+        for k, (t, p) in zip(geo, new):
+            out[f"label_to_{k}_t"], out[f"label_to_{k}_p"] = t, p
+        return out, labels

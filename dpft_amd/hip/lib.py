@@ -95,6 +95,25 @@ class LossLayer(C.Structure):
 
 LOSS_MAX_LAYERS = 8      # DPFT_LOSS_MAX_LAYERS
 
+
+class AugmentSample(C.Structure):
+    """dpft_augment_sample: one sample's augmentation parameters (canvas units of 1; include/dpft_hip.h)."""
+    _fields_ = [("a", C.c_float), ("bu", C.c_float), ("s", C.c_float), ("bv", C.c_float), ("gain", C.c_float * 4),
+                ("offset", C.c_float), ("delta_db", C.c_float), ("flip", C.c_int32), ("pad", C.c_int32)]
+
+
+class AugmentView(C.Structure):
+    _fields_ = [("T", C.c_void_p), ("P", C.c_void_p), ("T_out", C.c_void_p), ("P_out", C.c_void_p), ("shape", C.c_void_p),
+                ("shape_stride", C.c_int32), ("p_rows", C.c_int32), ("zoom", C.c_int32), ("pad", C.c_int32)]
+
+
+class AugmentLabels(C.Structure):
+    _fields_ = [("center", C.c_void_p), ("angle", C.c_void_p), ("center_out", C.c_void_p), ("angle_out", C.c_void_p),
+                ("rows", C.c_int32), ("pad", C.c_int32)]
+
+
+AUGMENT_CHUNK, AUGMENT_MAX_VIEWS = 8, 4      # DPFT_AUGMENT_CHUNK, DPFT_AUGMENT_MAX_VIEWS
+
 _P, _I, _L, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 _DESC = C.POINTER(ConvDesc)
 _PYR = C.POINTER(Pyramid)
@@ -191,6 +210,10 @@ SIGNATURES = {
     "dpft_resize_bilinear_nhwc_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dpft_resize_bilinear_nhwc_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dpft_scale_clip_f32": (_I, [_P, _P, _L, _F, _F, _F, _F, _P]),
+    "dpft_augment_camera_nhwc_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(AugmentSample), _P]),
+    "dpft_augment_camera_nhwc_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(AugmentSample), _P]),
+    "dpft_augment_radar_nhwc_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, C.POINTER(AugmentSample), _P]),
+    "dpft_augment_geometry_f32": (_I, [C.POINTER(AugmentView), _I, C.POINTER(AugmentLabels), C.POINTER(AugmentSample), _I, _P]),
     "dpft_detection_metrics_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _P, _P, _I, _I, _I, _I, _P]),
     "dpft_dataset_ap_scratch_bytes": (_L, [_I, _I, _I]),
     "dpft_dataset_ap_update_f32": (_I, [_P] * 9 + [_I, _P, _F, _P, _P, _L, _L, _P, _I, _I, _I, _I, _I, _P]),

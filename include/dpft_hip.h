@@ -869,6 +869,70 @@ int dpft_scale_clip_f32(const float* x, float* y, int64_t n, float in_lo, float 
                         float out_hi, dpft_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Training augmentation on the device (optional, "train.augment"; DESIGN.md section 3 "Training augmentation" states the
+ * coordinate contract): one horizontal flip per sample applied to every view and to the labels, a camera zoom / shift about
+ * the canvas centre, a photometric step on the camera frame and a gain on the radar maps.  The parameters are drawn on the
+ * HOST and passed as a host array of B samples; the entries copy them into the kernel arguments, DPFT_AUGMENT_CHUNK samples
+ * per launch (B above that: one launch per chunk) -- no device copy, no host wait, no allocation, stream-ordered.
+ *
+ * dpft_augment_sample: canvas coordinates in units of the canvas (u / W, v / H, edge convention):
+ *   u' = a u + bu,  v' = s v + bv;  s > 0 the zoom, a = s (a = -s and flip = 1 on a flipped sample, with bu already mirrored,
+ *   bu -> 1 - bu);  radar maps take only the flip.  gain[c] v + offset clipped to [0, 255] is the photometric step (all gains
+ *   1 and offset 0: skipped), delta_db is added to the radar maps before their scaling.
+ *
+ * camera: replaces the resize launch -- one thread per output pixel, C <= 4.  The centre of output pixel (x, y) goes through
+ *   the inverse map to the source; a pixel whose source centre lies outside [0, Ws] x [0, Hs] is written as 0, inside taps
+ *   clamp to the frame.  With s == 1, bv == 0 and bu == flip the result has the bits of the resize entries' output, or of that
+ *   output mirrored along x.
+ * radar: replaces dpft_scale_clip_f32 -- clip(((x + delta_db) - in_lo) / (in_hi - in_lo) * (out_hi - out_lo) + out_lo) read
+ *   from the mirrored index of axis 2 of (B,H,W,C) on a flipped sample; scale = 0: the flip alone.  delta_db = 0 and no flip
+ *   gives the bits of dpft_scale_clip_f32.
+ * geometry: one launch per chunk for all views and labels, OUT OF PLACE (the inputs are left as they are).  Per view
+ *   P' = M P diag(1,-1,1,1) and T' = F T F, F = diag(1,-1,1,1) (column negation and T' on flipped samples only; zeros keep
+ *   their sign); M = identity but M[0,0] = a, M[0,2] = bu W, M[1,1] = s, M[1,2] = bv H with (H, W) read from the view's int64
+ *   shape rows, on views with zoom = 1 (cameras); a = -1 / 1, bu W = W / 0 on the others.  Labels of a flipped sample:
+ *   center y and angle sin negated.  labels may be NULL; a sample with rows = 0 may have null pointers.
+ * ---------------------------------------------------------------------------------------- */
+#define DPFT_AUGMENT_CHUNK 8
+#define DPFT_AUGMENT_MAX_VIEWS 4
+typedef struct dpft_augment_sample {
+    float a, bu, s, bv;
+    float gain[4];
+    float offset;
+    float delta_db;
+    int32_t flip;
+    int32_t pad;
+} dpft_augment_sample;
+typedef struct dpft_augment_view {
+    const float* T;            /* (B,4,4) */
+    const float* P;            /* (B,p_rows,4) */
+    float* T_out;
+    float* P_out;
+    const int64_t* shape;      /* rows (H, W, ...) of shape_stride elements */
+    int32_t shape_stride;
+    int32_t p_rows;            /* 3 or 4 */
+    int32_t zoom;              /* 1: the zoom / shift part of M acts on this view (cameras) */
+    int32_t pad;
+} dpft_augment_view;
+typedef struct dpft_augment_labels {
+    const float* center;       /* (rows,3) */
+    const float* angle;        /* (rows,2) = [sin, cos] */
+    float* center_out;
+    float* angle_out;
+    int32_t rows;
+    int32_t pad;
+} dpft_augment_labels;
+int dpft_augment_camera_nhwc_f32(const float* src, float* dst, int32_t B, int32_t Hs, int32_t Ws, int32_t Hd, int32_t Wd,
+                                 int32_t C, const dpft_augment_sample* samples, dpft_stream_t stream);
+int dpft_augment_camera_nhwc_u8(const uint8_t* src, float* dst, int32_t B, int32_t Hs, int32_t Ws, int32_t Hd, int32_t Wd,
+                                int32_t C, const dpft_augment_sample* samples, dpft_stream_t stream);
+int dpft_augment_radar_nhwc_f32(const float* x, float* y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t scale,
+                                float in_lo, float in_hi, float out_lo, float out_hi, const dpft_augment_sample* samples,
+                                dpft_stream_t stream);
+int dpft_augment_geometry_f32(const dpft_augment_view* views, int32_t V, const dpft_augment_labels* labels,
+                              const dpft_augment_sample* samples, int32_t B, dpft_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-step detection metrics of the reference's train / validation loops (src/dprt/training/trainer.py:134,
  * src/dprt/evaluation/metric.py): mAP3D (IoU threshold, nelem-point "interpolated" curve, :16-151) and mGIoU3D
  * (:154-253) of every sample, on padded targets.  out (B,2) = (mAP, mGIoU) per sample (the caller applies the batch

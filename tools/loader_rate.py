@@ -9,6 +9,7 @@ the reference: torchvision.io.read_image) and np.load are then inside the worker
 
     python tools/loader_rate.py            -> one JSON line
     FILES=1 python tools/loader_rate.py    -> the same from files on disk
+    AUGMENT=1 python tools/loader_rate.py  -> with "train.augment" set (flip, camera zoom / shift / photometric, radar gain)
 """
 import copy, json, os, sys, time
 import torch
@@ -64,7 +65,11 @@ def main():
                                  fov=cfg["data"].get("fov"), image_size=cfg["data"].get("image_size", 512))
     else:
         ds = SyntheticRawDataset((steps + 12) * B, seed=3)
-    pre = GpuPreprocessor.from_config(cfg)
+    augment = os.environ.get("AUGMENT") == "1"
+    if augment:
+        cfg["train"]["augment"] = {"flip": 0.5, "camera": {"zoom": [0.9, 1.1], "shift": 0.05, "brightness": 0.2, "contrast": 0.2,
+                                                            "channel": 0.05}, "radar": {"gain_db": 3.0}}
+    pre = GpuPreprocessor.from_config(cfg, augment=True)
     loader, sampler = load_listed(ds, cfg, device=dev, preprocessor=pre, seed=1)
     it = iter(loader)
     batch, labels = next(it)
@@ -90,7 +95,7 @@ def main():
         tr.train_step(batch, labels)
     torch.cuda.synchronize()
     t_res = (time.perf_counter() - t0) / n
-    print(json.dumps({"workers": workers, "steps": n, "batch": B,
+    print(json.dumps({"workers": workers, "steps": n, "batch": B, "augment": cfg["train"].get("augment"),
                       "loader_in_the_loop_samples_per_s": B / t_loader, "loader_ms_per_step": 1e3 * t_loader,
                       "resident_batch_samples_per_s": B / t_res, "resident_ms_per_step": 1e3 * t_res,
                       "loader_over_resident": t_res / t_loader,
