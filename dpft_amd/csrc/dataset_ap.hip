@@ -18,6 +18,13 @@
 // the grouped finalize sums the frame rows per group (integers) and scans one workgroup per (group, class, combination) with two
 // block prefix sums per trip, membership and member-and-TP: the rank inside the group is the membership prefix.  Bin rule, suffix
 // maximum and summation order are ap_finalize_kernel's, so a group's table has the bits of an ungrouped run over its frames.
+//
+// True-positive errors (optional, the *_tp entries): the wave of the match pass that owns the reference combination keeps the target
+// index it took per sorted detection in LDS; the append loop turns every TP of that combination into four fp64 errors (centre
+// distance, height, size, heading) and writes them as int64 fixed point (rint(e * 2^32)) into a second store at the record's
+// position, zeros for every other record.  Integer sums are exact and order-free, so the finalize (one workgroup per class, or per
+// (group, class): block scan of the TP bit and of the four integers, cumulative means at the recall points) gives a group the bits
+// of an ungrouped run over its frames, and a merge of ranks cannot move a bit.
 #include "common.h"
 #include "box_iou.h"
 
@@ -27,8 +34,8 @@ namespace dpft {
 
 constexpr int kApMaxN = 1024, kApMaxM = 256, kApMaxC = 16, kApMaxK = 8, kApMaxR = 101;
 // counters (int64): [0] record cursor, [1] queries dropped for a NaN score, [2] records refused for lack of capacity,
-// [16 + c] ground-truth count of class c
-constexpr int kApCursor = 0, kApNan = 1, kApOverflow = 2, kApNpos = 16;
+// [3] true-positive errors that did not fit the fixed point (the *_tp entries only), [16 + c] ground-truth count of class c
+constexpr int kApCursor = 0, kApNan = 1, kApOverflow = 2, kApTpSat = 3, kApNpos = 16;
 
 struct ApArgs {
     const float *cls, *center, *size, *angle;      // (B,N,C) (B,N,3) (B,N,3) (B,N,2)
@@ -87,6 +94,38 @@ __device__ __forceinline__ unsigned ap_group_mask(const ApGroupArgs& g, int b) {
     return mask;
 }
 
+struct ApTpArgs {
+    long long* err;                                // (capacity, 4): ate, aze, ase, aoe as rint(e * 2^32) at the record's position
+    int ref_k;                                     // the reference combination
+    int fold_pi;                                   // aoe = min(aoe, pi - aoe)
+};
+
+constexpr double kApTpScale = 4294967296.0, kApTpLimit = 1048576.0;      // 2^32 units per metre (or radian); |e| < 2^20
+constexpr long long kApTpSaturated = 1ll << 52;
+
+// The four errors of a (detection, target) pair in fp64 straight from the fp32 inputs; the operation order is part of the
+// definition (dpft_amd/evaluation/dataset_ap.py; tests/dataset_ap_tp_ref.py restates it).
+__device__ inline void ap_tp_errors(const float* ce1, const float* sz1, const float* an1, const float* ce2, const float* sz2,
+                                    const float* an2, int fold_pi, double* e) {
+    const double dx = (double)ce1[0] - (double)ce2[0], dy = (double)ce1[1] - (double)ce2[1];
+    e[0] = sqrt(dx * dx + dy * dy);
+    e[1] = fabs((double)ce1[2] - (double)ce2[2]);
+    const double l1 = sz1[0], w1 = sz1[1], h1 = sz1[2], l2 = sz2[0], w2 = sz2[1], h2 = sz2[2];
+    const double P = fmin(l1, l2) * fmin(w1, w2) * fmin(h1, h2);
+    const double v1 = l1 * w1 * h1, v2 = l2 * w2 * h2;
+    e[2] = 1.0 - P / (v1 + v2 - P);
+    const double r1 = hypot((double)an1[0], (double)an1[1]), r2 = hypot((double)an2[0], (double)an2[1]);
+    const double s1 = (double)an1[0] / r1, c1 = (double)an1[1] / r1, s2 = (double)an2[0] / r2, c2 = (double)an2[1] / r2;
+    const double t = atan2(fabs(s1 * c2 - c1 * s2), c1 * c2 + s1 * s2);
+    e[3] = fold_pi ? fmin(t, 3.141592653589793 - t) : t;
+}
+
+// rint(e * 2^32), half to even; a value that is not finite or not below 2^20 in magnitude stores 2^52 and counts in `sat`
+__device__ __forceinline__ long long ap_tp_quantise(double e, int& sat) {
+    if (!(fabs(e) < kApTpLimit)) { ++sat; return kApTpSaturated; }
+    return (long long)rint(e * kApTpScale);
+}
+
 __device__ __forceinline__ bool ap_in_roi(const ApArgs& a, const float* c) {
     if (!a.has_roi) return true;
     return (a.roi[0] < c[0]) && (c[0] < a.roi[1]) && (a.roi[2] < c[1]) && (c[1] < a.roi[3]) && (a.roi[4] < c[2]) && (c[2] < a.roi[5]);
@@ -110,13 +149,15 @@ __global__ __launch_bounds__(128) void ap_pair_kernel(ApArgs a) {
     a.pair[idx * 2 + 1] = d3;
 }
 
-// `g` is a compile-time null in ap_match_kernel: the frame row below exists in ap_match_groups_kernel only
-__device__ __forceinline__ void ap_match_body(const ApArgs& a, const ApGroupArgs* g) {
+// `g` is a compile-time null in ap_match_kernel: the frame row below exists in the *_groups kernels only; `t` is one in the kernels
+// without true-positive errors: the matched target index and the error rows exist in the *_tp kernels only
+__device__ __forceinline__ void ap_match_body(const ApArgs& a, const ApGroupArgs* g, const ApTpArgs* t) {
     __shared__ unsigned long long key[kApMaxN];      // (score descending, query ascending) as one ascending integer
     __shared__ float score[kApMaxN];
     __shared__ unsigned tp[kApMaxN];                 // per sorted detection: bit k = TP of combination k
     __shared__ unsigned char label[kApMaxN];
     __shared__ unsigned char cand[kApMaxN];          // per sorted detection: bit k = some target lies above threshold k
+    __shared__ unsigned char match[kApMaxN];         // per sorted detection: the target the reference combination took (t only)
     __shared__ int npos[kApMaxC];
     __shared__ int s_D, s_nan;
     __shared__ long long s_base;
@@ -200,6 +241,7 @@ __device__ __forceinline__ void ap_match_body(const ApArgs& a, const ApGroupArgs
             if (bj != INT_MAX) {
                 if (lane == (bj & 63)) assigned |= 1u << (bj >> 6);
                 if (lane == 0) atomicOr(&tp[i], 1u << k);
+                if (t && k == t->ref_k && lane == 0) match[i] = (unsigned char)bj;
             }
         }
     }
@@ -217,6 +259,21 @@ __device__ __forceinline__ void ap_match_body(const ApArgs& a, const ApGroupArgs
         if (pos >= a.capacity) { atomicAdd(a.counters + kApOverflow, 1ull); continue; }      // (the host sizes the store: never)
         const int q = (int)(unsigned)key[i];
         a.records[pos] = make_int4((int)__float_as_uint(score[q]), a.first_frame + b, q | ((int)label[q] << 16), (int)tp[i]);
+        if (t) {                                                        // (non-TP rows are zeros: no stale bytes travel)
+            long long v[4] = {0, 0, 0, 0};
+            if ((tp[i] >> t->ref_k) & 1u) {
+                const float* gb = a.gt_box + ((int64_t)b * a.Mmax + match[i]) * 8;
+                const int64_t bn = (int64_t)b * N + q;
+                double e[4];
+                int sat = 0;
+                ap_tp_errors(a.center + bn * 3, a.size + bn * 3, a.angle + bn * 2, gb, gb + 3, gb + 6, t->fold_pi, e);
+                for (int x = 0; x < 4; ++x) v[x] = ap_tp_quantise(e[x], sat);
+                if (sat) atomicAdd(a.counters + kApTpSat, (unsigned long long)sat);
+            }
+            longlong2* row = reinterpret_cast<longlong2*>(t->err + pos * 4);
+            row[0] = make_longlong2(v[0], v[1]);
+            row[1] = make_longlong2(v[2], v[3]);
+        }
     }
     if (g && tid < kApFrameRow) {                                       // (the host sized the frame store: frame_base + B rows fit)
         int32_t* row = g->frames + (g->frame_base + b) * kApFrameRow;
@@ -224,9 +281,13 @@ __device__ __forceinline__ void ap_match_body(const ApArgs& a, const ApGroupArgs
     }
 }
 
-__global__ __launch_bounds__(256) void ap_match_kernel(ApArgs a) { ap_match_body(a, nullptr); }
+__global__ __launch_bounds__(256) void ap_match_kernel(ApArgs a) { ap_match_body(a, nullptr, nullptr); }
 
-__global__ __launch_bounds__(256) void ap_match_groups_kernel(ApArgs a, ApGroupArgs g) { ap_match_body(a, &g); }
+__global__ __launch_bounds__(256) void ap_match_groups_kernel(ApArgs a, ApGroupArgs g) { ap_match_body(a, &g, nullptr); }
+
+__global__ __launch_bounds__(256) void ap_match_tp_kernel(ApArgs a, ApTpArgs t) { ap_match_body(a, nullptr, &t); }
+
+__global__ __launch_bounds__(256) void ap_match_groups_tp_kernel(ApArgs a, ApGroupArgs g, ApTpArgs t) { ap_match_body(a, &g, &t); }
 
 struct ApFinalArgs {
     const int4* rec;                       // ordered by (class, score desc, frame, query)
@@ -382,6 +443,99 @@ __global__ __launch_bounds__(256) void ap_finalize_groups_kernel(ApGroupFinalArg
     }
 }
 
+struct ApTpFinalArgs {
+    const int4* rec;                       // ordered by (class, score desc, frame, query)
+    const long long* err;                  // (n, 4): the error rows in the same order
+    const unsigned* rec_groups;            // (n) group mask of every record's frame, or null: every record is a member
+    const long long* class_start;          // (C + 1)
+    const unsigned long long* counters;    // ground truth per class (without groups)
+    const double* group_npos;              // (G, C-1) ground truth per group and class (with groups)
+    double *tp_err, *tp_points;            // (G, C-1, 4) (G, C-1)
+    long long n;
+    int G, C, k, R, i_min;
+};
+
+// One workgroup per (group, class).  T = TPs of the reference combination so far, S = their integer error sums so far (inclusive
+// block scans, carried across trips of 256 records); the TP with count T serves the recall points floor((T-1) R / npos) < i <=
+// floor(T R / npos) with the cumulative means S / 2^32 / T: every point has one writer.  The class's error is the mean of the
+// served points i >= i_min, summed in ascending i.
+__global__ __launch_bounds__(256) void ap_finalize_tp_kernel(ApTpFinalArgs a) {
+    __shared__ double table[(kApMaxR + 1) * 4];
+    __shared__ unsigned char served[kApMaxR + 1];
+    __shared__ int wmem[4], wtp[4];
+    __shared__ unsigned long long wsum[4][4];
+    const int c = 1 + blockIdx.x % (a.C - 1), g = blockIdx.x / (a.C - 1), k = a.k;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long s = min(max(a.class_start[c], 0ll), a.n), e = min(max(a.class_start[c + 1], s), a.n);
+    const long long np = a.rec_groups ? (long long)a.group_npos[g * (a.C - 1) + c - 1] : (long long)a.counters[kApNpos + c];
+    for (int i = tid; i <= a.R; i += 256) served[i] = 0;
+    __syncthreads();
+    long long carry = 0;
+    unsigned long long csum[4] = {0ull, 0ull, 0ull, 0ull};              // (unsigned: a sum of saturated rows may wrap, the host
+    for (long long base = s; base < e; base += 256) {                  //  reports those as NaN)
+        const long long p = base + tid;
+        const bool mem = p < e && (!a.rec_groups || ((a.rec_groups[p] >> g) & 1u));
+        const bool bit = mem && ((a.rec[p].w >> k) & 1);
+        unsigned long long v[4] = {0ull, 0ull, 0ull, 0ull};
+        if (bit) {
+            const longlong2* row = reinterpret_cast<const longlong2*>(a.err + p * 4);
+            const longlong2 r0 = row[0], r1 = row[1];
+            v[0] = (unsigned long long)r0.x; v[1] = (unsigned long long)r0.y;
+            v[2] = (unsigned long long)r1.x; v[3] = (unsigned long long)r1.y;
+        }
+        for (int o = 1; o < 64; o <<= 1) {                              // inclusive scan over the wave
+#pragma unroll
+            for (int x = 0; x < 4; ++x) {
+                const unsigned long long u = __shfl_up(v[x], o);
+                if (lane >= o) v[x] += u;
+            }
+        }
+        const unsigned long long bal = __ballot(bit);
+        if (lane == 63) {
+#pragma unroll
+            for (int x = 0; x < 4; ++x) wsum[wave][x] = v[x];
+        }
+        if (lane == 0) wtp[wave] = __popcll(bal);
+        __syncthreads();
+        int off = 0, tot = 0;
+        unsigned long long osum[4] = {0ull, 0ull, 0ull, 0ull}, tsum[4] = {0ull, 0ull, 0ull, 0ull};
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) off += wtp[w];
+            tot += wtp[w];
+#pragma unroll
+            for (int x = 0; x < 4; ++x) {
+                if (w < wave) osum[x] += wsum[w][x];
+                tsum[x] += wsum[w][x];
+            }
+        }
+        if (bit && np > 0) {
+            const long long T = carry + off + __popcll(bal & ((2ull << lane) - 1ull));
+            const long long lo = (T - 1) * a.R / np;
+            long long hi = T * a.R / np;
+            if (hi > a.R) hi = a.R;
+            for (long long i = lo + 1; i <= hi; ++i) {
+#pragma unroll
+                for (int x = 0; x < 4; ++x)
+                    table[i * 4 + x] = (double)(long long)(csum[x] + osum[x] + v[x]) / kApTpScale / (double)T;
+                served[i] = 1;
+            }
+        }
+        carry += tot;
+#pragma unroll
+        for (int x = 0; x < 4; ++x) csum[x] += tsum[x];
+        __syncthreads();
+    }
+    if (tid < 4) {
+        double sum = 0;
+        int count = 0;
+        for (int i = a.i_min; i <= a.R; ++i)
+            if (served[i]) { sum += table[i * 4 + tid]; ++count; }
+        const int o = g * (a.C - 1) + c - 1;
+        a.tp_err[o * 4 + tid] = count > 0 ? sum / (double)count : __longlong_as_double(0x7ff8000000000000ll);
+        if (tid == 0) a.tp_points[o] = (double)count;
+    }
+}
+
 static bool ap_sizes_ok(int B, int N, int Mmax, int C) {
     return B > 0 && N > 0 && N <= kApMaxN && Mmax > 0 && Mmax <= kApMaxM && C >= 2 && C <= kApMaxC;
 }
@@ -435,12 +589,22 @@ static int ap_fill_update(ApArgs& a, const float* cls, const float* center, cons
     return DPFT_OK;
 }
 
-extern "C" int dpft_dataset_ap_update_f32(const float* cls, const float* center, const float* size, const float* angle,
-                                          const float* gt_box, const int32_t* gt_id, const int32_t* counts,
-                                          const double* iou_thrs, const int32_t* kinds, int32_t K, const float* roi6,
-                                          float min_score, void* scratch, void* records, int64_t capacity, int64_t reserved,
-                                          int64_t* counters, int32_t first_frame, int32_t B, int32_t N, int32_t Mmax,
-                                          int32_t C, dpft_stream_t stream) {
+// the true-positive arguments of the *_tp entries (checked before anything is launched)
+static int ap_fill_tp(ApTpArgs& t, void* tp_errors, int32_t ref_k, int32_t fold_pi, int32_t K) {
+    DPFT_REQUIRE(tp_errors, "dataset_ap_update_tp: null argument");
+    DPFT_REQUIRE(((uintptr_t)tp_errors & 15) == 0, "dataset_ap_update_tp: the error rows need 16-byte alignment");
+    DPFT_REQUIRE(ref_k >= 0 && ref_k < K, "dataset_ap_update_tp: the reference combination must be one of the %d, got %d", K, ref_k);
+    DPFT_REQUIRE(fold_pi == 0 || fold_pi == 1, "dataset_ap_update_tp: fold_pi must be 0 or 1, got %d", fold_pi);
+    t.err = (long long*)tp_errors; t.ref_k = ref_k; t.fold_pi = fold_pi;
+    return DPFT_OK;
+}
+
+// the two launches of an update without groups; `t` = null: no true-positive errors
+static int ap_update(const float* cls, const float* center, const float* size, const float* angle, const float* gt_box,
+                     const int32_t* gt_id, const int32_t* counts, const double* iou_thrs, const int32_t* kinds, int32_t K,
+                     const float* roi6, float min_score, void* scratch, void* records, int64_t capacity, int64_t reserved,
+                     int64_t* counters, int32_t first_frame, int32_t B, int32_t N, int32_t Mmax, int32_t C, const ApTpArgs* t,
+                     dpft_stream_t stream) {
     ApArgs a;
     int rc = ap_fill_update(a, cls, center, size, angle, gt_box, gt_id, counts, iou_thrs, kinds, K, roi6, min_score, scratch, records,
                             capacity, reserved, counters, first_frame, B, N, Mmax, C);
@@ -449,20 +613,42 @@ extern "C" int dpft_dataset_ap_update_f32(const float* cls, const float* center,
     hipLaunchKernelGGL(ap_pair_kernel, dim3(cdiv(total, 128)), dim3(128), 0, (hipStream_t)stream, a);
     rc = check_launch("dataset_ap_update pairs");
     if (rc) return rc;
-    hipLaunchKernelGGL(ap_match_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
+    if (t) hipLaunchKernelGGL(ap_match_tp_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a, *t);
+    else hipLaunchKernelGGL(ap_match_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
     return check_launch("dataset_ap_update");
 }
 
-extern "C" int dpft_dataset_ap_update_groups_f32(const float* cls, const float* center, const float* size, const float* angle,
-                                                 const float* gt_box, const int32_t* gt_id, const int32_t* counts,
-                                                 const double* iou_thrs, const int32_t* kinds, int32_t K, const float* roi6,
-                                                 float min_score, void* scratch, void* records, int64_t capacity,
-                                                 int64_t reserved, int64_t* counters, int32_t first_frame, int32_t B, int32_t N,
-                                                 int32_t Mmax, int32_t C, const void* const* desc_ptrs,
-                                                 const int32_t* desc_types, const double* desc_host, const int32_t* axis_cols,
-                                                 const int32_t* axis_counts, const int32_t* axis_values, int32_t n_axes,
-                                                 void* frames, int64_t frame_capacity, int64_t frames_before,
-                                                 dpft_stream_t stream) {
+extern "C" int dpft_dataset_ap_update_f32(const float* cls, const float* center, const float* size, const float* angle,
+                                          const float* gt_box, const int32_t* gt_id, const int32_t* counts,
+                                          const double* iou_thrs, const int32_t* kinds, int32_t K, const float* roi6,
+                                          float min_score, void* scratch, void* records, int64_t capacity, int64_t reserved,
+                                          int64_t* counters, int32_t first_frame, int32_t B, int32_t N, int32_t Mmax,
+                                          int32_t C, dpft_stream_t stream) {
+    return ap_update(cls, center, size, angle, gt_box, gt_id, counts, iou_thrs, kinds, K, roi6, min_score, scratch, records, capacity,
+                     reserved, counters, first_frame, B, N, Mmax, C, nullptr, stream);
+}
+
+extern "C" int dpft_dataset_ap_update_tp_f32(const float* cls, const float* center, const float* size, const float* angle,
+                                             const float* gt_box, const int32_t* gt_id, const int32_t* counts,
+                                             const double* iou_thrs, const int32_t* kinds, int32_t K, const float* roi6,
+                                             float min_score, void* scratch, void* records, int64_t capacity, int64_t reserved,
+                                             int64_t* counters, int32_t first_frame, int32_t B, int32_t N, int32_t Mmax,
+                                             int32_t C, void* tp_errors, int32_t ref_k, int32_t fold_pi, dpft_stream_t stream) {
+    ApTpArgs t;
+    int rc = ap_fill_tp(t, tp_errors, ref_k, fold_pi, K);
+    if (rc) return rc;
+    return ap_update(cls, center, size, angle, gt_box, gt_id, counts, iou_thrs, kinds, K, roi6, min_score, scratch, records, capacity,
+                     reserved, counters, first_frame, B, N, Mmax, C, &t, stream);
+}
+
+// the two launches of an update with groups; `t` = null: no true-positive errors
+static int ap_update_groups(const float* cls, const float* center, const float* size, const float* angle, const float* gt_box,
+                            const int32_t* gt_id, const int32_t* counts, const double* iou_thrs, const int32_t* kinds, int32_t K,
+                            const float* roi6, float min_score, void* scratch, void* records, int64_t capacity, int64_t reserved,
+                            int64_t* counters, int32_t first_frame, int32_t B, int32_t N, int32_t Mmax, int32_t C,
+                            const void* const* desc_ptrs, const int32_t* desc_types, const double* desc_host,
+                            const int32_t* axis_cols, const int32_t* axis_counts, const int32_t* axis_values, int32_t n_axes,
+                            void* frames, int64_t frame_capacity, int64_t frames_before, const ApTpArgs* t, dpft_stream_t stream) {
     DPFT_REQUIRE(desc_ptrs && desc_types && frames, "dataset_ap_update_groups: null argument");
     DPFT_REQUIRE(n_axes == 0 || (axis_cols && axis_counts && axis_values), "dataset_ap_update_groups: null axis tables");
     ApArgs a;
@@ -507,8 +693,35 @@ extern "C" int dpft_dataset_ap_update_groups_f32(const float* cls, const float* 
     hipLaunchKernelGGL(ap_pair_kernel, dim3(cdiv(total, 128)), dim3(128), 0, (hipStream_t)stream, a);
     rc = check_launch("dataset_ap_update_groups pairs");
     if (rc) return rc;
-    hipLaunchKernelGGL(ap_match_groups_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a, g);
+    if (t) hipLaunchKernelGGL(ap_match_groups_tp_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a, g, *t);
+    else hipLaunchKernelGGL(ap_match_groups_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a, g);
     return check_launch("dataset_ap_update_groups");
+}
+
+extern "C" int dpft_dataset_ap_update_groups_f32(const float* cls, const float* center, const float* size, const float* angle,
+        const float* gt_box, const int32_t* gt_id, const int32_t* counts, const double* iou_thrs, const int32_t* kinds, int32_t K,
+        const float* roi6, float min_score, void* scratch, void* records, int64_t capacity, int64_t reserved, int64_t* counters,
+        int32_t first_frame, int32_t B, int32_t N, int32_t Mmax, int32_t C, const void* const* desc_ptrs, const int32_t* desc_types,
+        const double* desc_host, const int32_t* axis_cols, const int32_t* axis_counts, const int32_t* axis_values, int32_t n_axes,
+        void* frames, int64_t frame_capacity, int64_t frames_before, dpft_stream_t stream) {
+    return ap_update_groups(cls, center, size, angle, gt_box, gt_id, counts, iou_thrs, kinds, K, roi6, min_score, scratch, records,
+                            capacity, reserved, counters, first_frame, B, N, Mmax, C, desc_ptrs, desc_types, desc_host, axis_cols,
+                            axis_counts, axis_values, n_axes, frames, frame_capacity, frames_before, nullptr, stream);
+}
+
+extern "C" int dpft_dataset_ap_update_groups_tp_f32(const float* cls, const float* center, const float* size, const float* angle,
+        const float* gt_box, const int32_t* gt_id, const int32_t* counts, const double* iou_thrs, const int32_t* kinds, int32_t K,
+        const float* roi6, float min_score, void* scratch, void* records, int64_t capacity, int64_t reserved, int64_t* counters,
+        int32_t first_frame, int32_t B, int32_t N, int32_t Mmax, int32_t C, const void* const* desc_ptrs, const int32_t* desc_types,
+        const double* desc_host, const int32_t* axis_cols, const int32_t* axis_counts, const int32_t* axis_values, int32_t n_axes,
+        void* frames, int64_t frame_capacity, int64_t frames_before, void* tp_errors, int32_t ref_k, int32_t fold_pi,
+        dpft_stream_t stream) {
+    ApTpArgs t;
+    int rc = ap_fill_tp(t, tp_errors, ref_k, fold_pi, K);
+    if (rc) return rc;
+    return ap_update_groups(cls, center, size, angle, gt_box, gt_id, counts, iou_thrs, kinds, K, roi6, min_score, scratch, records,
+                            capacity, reserved, counters, first_frame, B, N, Mmax, C, desc_ptrs, desc_types, desc_host, axis_cols,
+                            axis_counts, axis_values, n_axes, frames, frame_capacity, frames_before, &t, stream);
 }
 
 extern "C" int dpft_dataset_ap_finalize_f64(const void* records_sorted, int64_t n_records, const int64_t* class_start,
@@ -549,4 +762,42 @@ extern "C" int dpft_dataset_ap_finalize_groups_f64(const void* records_sorted, c
     if (rc) return rc;
     hipLaunchKernelGGL(ap_finalize_groups_kernel, dim3(G * (C - 1) * K), dim3(256), 0, (hipStream_t)stream, a);
     return check_launch("dataset_ap_finalize_groups");
+}
+
+// argument checks and launch shared by the two true-positive finalize entries (record_groups = null: without groups)
+static int ap_finalize_tp(const char* who, const void* records_sorted, const int64_t* tp_errors_sorted, const uint32_t* record_groups,
+                          int64_t n_records, const int64_t* class_start, const int64_t* counters, const double* group_npos, int32_t G,
+                          int32_t C, int32_t ref_k, int32_t R, int32_t i_min, double* tp_err, double* tp_points,
+                          dpft_stream_t stream) {
+    DPFT_REQUIRE(records_sorted && tp_errors_sorted && class_start && tp_err && tp_points, "%s: null argument", who);
+    DPFT_REQUIRE(n_records >= 0 && C >= 2 && C <= kApMaxC && ref_k >= 0 && ref_k < kApMaxK && R >= 2 && R <= kApMaxR,
+                 "%s: sizes out of range (2 <= C <= %d, 0 <= ref_k < %d, 2 <= R <= %d)", who, kApMaxC, kApMaxK, kApMaxR);
+    DPFT_REQUIRE(i_min >= 1 && i_min <= R, "%s: the first recall point must lie in 1..R, got %d", who, i_min);
+    DPFT_REQUIRE(G >= 1 && G <= kApMaxGroups, "%s: 1..%d groups, got %d", who, kApMaxGroups, G);
+    DPFT_REQUIRE(((uintptr_t)records_sorted & 15) == 0 && ((uintptr_t)tp_errors_sorted & 15) == 0,
+                 "%s: records and error rows need 16-byte alignment", who);
+    ApTpFinalArgs a;
+    memset(&a, 0, sizeof(a));
+    a.rec = (const int4*)records_sorted; a.err = (const long long*)tp_errors_sorted; a.rec_groups = record_groups;
+    a.class_start = (const long long*)class_start; a.counters = (const unsigned long long*)counters; a.group_npos = group_npos;
+    a.tp_err = tp_err; a.tp_points = tp_points; a.n = n_records; a.G = G; a.C = C; a.k = ref_k; a.R = R; a.i_min = i_min;
+    hipLaunchKernelGGL(ap_finalize_tp_kernel, dim3(G * (C - 1)), dim3(256), 0, (hipStream_t)stream, a);
+    return check_launch(who);
+}
+
+extern "C" int dpft_dataset_ap_finalize_tp_f64(const void* records_sorted, const int64_t* tp_errors_sorted, int64_t n_records,
+                                               const int64_t* class_start, const int64_t* counters, int32_t C, int32_t ref_k,
+                                               int32_t R, int32_t i_min, double* tp_err, double* tp_points, dpft_stream_t stream) {
+    DPFT_REQUIRE(counters, "dataset_ap_finalize_tp: null argument");
+    return ap_finalize_tp("dataset_ap_finalize_tp", records_sorted, tp_errors_sorted, nullptr, n_records, class_start, counters,
+                          nullptr, 1, C, ref_k, R, i_min, tp_err, tp_points, stream);
+}
+
+extern "C" int dpft_dataset_ap_finalize_tp_groups_f64(const void* records_sorted, const int64_t* tp_errors_sorted,
+                                                      const uint32_t* record_groups, int64_t n_records, const int64_t* class_start,
+                                                      const double* group_npos, int32_t G, int32_t C, int32_t ref_k, int32_t R,
+                                                      int32_t i_min, double* tp_err, double* tp_points, dpft_stream_t stream) {
+    DPFT_REQUIRE(record_groups && group_npos, "dataset_ap_finalize_tp_groups: null argument");
+    return ap_finalize_tp("dataset_ap_finalize_tp_groups", records_sorted, tp_errors_sorted, record_groups, n_records, class_start,
+                          nullptr, group_npos, G, C, ref_k, R, i_min, tp_err, tp_points, stream);
 }

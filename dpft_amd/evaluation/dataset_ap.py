@@ -42,10 +42,40 @@ that owns a frame also writes one row of a frame store (frame, group bitmask, np
 and no copy: device tensors travel as pointers by value, host tensors as values in the kernel arguments (only a device
 description that is neither contiguous nor fp32 / fp64 / int32 / int64 costs a conversion).  ``dpft_dataset_ap_finalize_groups_f64``
 (two launches per epoch) replaces the finalize entry; its ``all`` group has the bits of the ungrouped table.
+
+True-positive errors (``tp_errors``; tests/dataset_ap_tp_ref.py restates them with plain loops).  What is wrong with the boxes
+that do match: translation in the ground plane, height, size, heading.  Matching stays the IoU rule above -- NOT a centre distance:
+the numbers are not nuScenes' TP metrics and not K-Radar's, they only share the idea.
+
+* ``tp_errors``: true, or {"at": [kind, iou], "min_recall": 0.1, "angle_period": "2pi" | "pi"}.  ``at`` is the reference
+  combination and must be one of the configured ones; default = the first kind with the smallest threshold (the loosest match).
+  A TP of the reference combination is exactly the (detection, target) pair the greedy walk above makes for it.
+* Per TP, in fp64 straight from the fp32 inputs, in this operation order (d = detection, g = target):
+  ``ate`` = sqrt(dx * dx + dy * dy), metres;  ``aze`` = |z_d - z_g|, metres;
+  ``ase`` = 1 - P / (Vd + Vg - P) with P = min(l_d, l_g) * min(w_d, w_g) * min(h_d, h_g) and V = l * w * h, both multiplied left
+  to right (one minus the IoU after aligning centre and heading);
+  ``aoe`` = atan2(|s1 * c2 - c1 * s2|, c1 * c2 + s1 * s2) on the pairs (s, c) = (sin, cos) / hypot(sin, cos), in [0, pi];
+  ``angle_period: "pi"`` makes it min(aoe, pi - aoe) (a box and its reverse count as the same).
+* Each error is stored as the int64 q = rint(e * 2^32) (half to even): sums over TPs are exact and independent of order, so a
+  group's table has the bits of an ungrouped run over its frames and a merge of ranks cannot move a bit.  An error that is not
+  finite or whose magnitude is >= 2^20 stores 2^52 and counts in ``tp_saturated``; if that is non-zero every TP-error key is NaN.
+* Per class over the records in (score desc, frame, query) order: T = running TP count of the reference combination, S_e =
+  running integer sum of error e.  The TP with count T serves the recall points i (1..R) with floor((T - 1) * R / npos) < i <=
+  min(floor(T * R / npos), R) (integers); the value there is float64(S_e) / 2^32 / float64(T), the cumulative mean.  The class's
+  error is the mean of the served points with i >= i_min = max(1, ceil(min_recall * R)) (exact, from the decimal form of
+  ``min_recall``: 0.1 * 40 gives 4), summed in ascending i and divided by their count; NaN when npos = 0 or no point is served.
+* ``ATE/{c}``, ``AZE/{c}``, ``ASE/{c}``, ``AOE/{c}``, their means ``mATE`` .. ``mAOE`` over the classes that are not NaN,
+  ``tp_points/{c}`` (served points averaged), ``tp_saturated``; with groups the same keys per group with the AP keys' suffix.
+
+Device side with ``tp_errors``: ``dpft_dataset_ap_update_tp_f32`` / ``_groups_tp_f32`` instead of the update entries -- the SAME two
+launches; the wave that owns the reference combination keeps the target it took, and the append loop writes one row of four
+int64 into a second store at the record's position (zeros for a non-TP).  ``dpft_dataset_ap_finalize_tp_f64`` / ``_tp_groups_f64``
+(one launch) runs beside the finalize entry on the error rows gathered by the records' sort permutation.
 """
 from __future__ import annotations
 
 import math
+from fractions import Fraction
 from typing import Any, Dict, List, Optional, Sequence
 
 import torch
@@ -54,7 +84,9 @@ KINDS = ("bev", "3d")
 DEFAULT_ROI = (0.0, 72.0, -6.4, 6.4, -2.0, 6.0)      # the exporter's field of view (csrc/export.hip)
 MAX_COMBINATIONS = 8
 N_COUNTERS = 32
-CURSOR, DROPPED_NAN, OVERFLOW, NPOS = 0, 1, 2, 16    # layout of the int64 counters (include/dpft_hip.h)
+CURSOR, DROPPED_NAN, OVERFLOW, TP_SATURATED, NPOS = 0, 1, 2, 3, 16      # layout of the int64 counters (include/dpft_hip.h)
+TP_ERRORS = ("ATE", "AZE", "ASE", "AOE")             # the columns of the error rows
+ANGLE_PERIODS = ("2pi", "pi")
 _DEFAULT = object()
 AXES = ("time", "road", "weather")                   # the exporter's order (exporters/kradar.py _serialize_description)
 _AXIS_COLUMN = {"road": 0, "time": 1, "weather": 2}  # description = [road, time, weather]
@@ -76,6 +108,38 @@ def _parse_groups(groups: Any) -> List[str]:
             or len(set(axes)) != len(axes) or any(a not in AXES for a in axes):
         raise ValueError(f"dataset_ap: 'groups' must be true or a non-empty list of distinct axes out of {AXES}, got {groups!r}")
     return [a for a in AXES if a in axes]
+
+
+def _parse_tp_errors(spec: Any, combinations: Sequence[tuple], kinds: Sequence[str], iou: Sequence[float],
+                     recall_points: int) -> Optional[Dict[str, Any]]:
+    """None / False -> None; True -> the defaults; a dict of at / min_recall / angle_period -> the parameters: ``at`` (kind,
+    threshold), ``k`` its index among the combinations, ``min_recall``, ``i_min`` and ``angle_period``."""
+    if spec is None or spec is False:
+        return None
+    if spec is True:
+        spec = {}
+    if not isinstance(spec, dict):
+        raise ValueError(f"dataset_ap: 'tp_errors' must be true or a dict of at / min_recall / angle_period, got {spec!r}")
+    unknown = sorted(set(spec) - {"at", "min_recall", "angle_period"})
+    if unknown:
+        raise ValueError(f"dataset_ap: 'tp_errors' has unknown key(s) {unknown} (at, min_recall, angle_period)")
+    at = spec.get("at")
+    if at is None:
+        at = (kinds[0], min(iou))
+    ok = isinstance(at, (list, tuple)) and len(at) == 2 and isinstance(at[0], str) and isinstance(at[1], (int, float)) \
+        and not isinstance(at[1], bool)
+    if not ok or (at[0], float(at[1])) not in combinations:
+        raise ValueError(f"dataset_ap: tp_errors 'at' must be one of the combinations {list(combinations)}, got {at!r}")
+    at = (at[0], float(at[1]))
+    min_recall = spec.get("min_recall", 0.1)
+    if isinstance(min_recall, bool) or not isinstance(min_recall, (int, float)) or not 0.0 <= float(min_recall) <= 1.0:
+        raise ValueError(f"dataset_ap: tp_errors 'min_recall' must be a number in [0, 1], got {min_recall!r}")
+    period = spec.get("angle_period", "2pi")
+    if not isinstance(period, str) or period not in ANGLE_PERIODS:
+        raise ValueError(f"dataset_ap: tp_errors 'angle_period' must be one of {ANGLE_PERIODS}, got {period!r}")
+    # exact: the decimal form of the number times R, so that 0.1 * 40 is 4 and not the 4.000000000000000222 of its binary form
+    i_min = max(1, math.ceil(Fraction(repr(float(min_recall))) * recall_points))
+    return {"at": at, "k": list(combinations).index(at), "min_recall": float(min_recall), "i_min": i_min, "angle_period": period}
 
 
 def _axis_tables(axes: Sequence[str], mappings: Optional[Dict[str, Any]]) -> Dict[str, List[tuple]]:
@@ -117,8 +181,8 @@ def _gather_rows(rows: torch.Tensor) -> torch.Tensor:
 def gather_state(state: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """The collective behind ``DatasetAP.all_gather`` on a raw ``state()``: record counts all-gathered, records all-gathered
     padded to the maximum count and concatenated in rank order, counters all-reduced (the cursor becomes the total count).  The
-    frame rows of a grouped accumulator (``frames``, when the state has them) are gathered like the records.  The tensors stay
-    on the device they are on."""
+    frame rows of a grouped accumulator (``frames``) and the true-positive error rows (``tp_errors``), when the state has them, are
+    gathered like the records.  The tensors stay on the device they are on."""
     import torch.distributed as dist
     records, counters = state["records"], state["counters"].clone()
     out = {"records": _gather_rows(records)}
@@ -127,18 +191,22 @@ def gather_state(state: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     out["counters"] = counters
     if "frames" in state:
         out["frames"] = _gather_rows(state["frames"])
+    if "tp_errors" in state:
+        out["tp_errors"] = _gather_rows(state["tp_errors"])
     return out
 
 
 class DatasetAP:
     def __init__(self, num_classes: int, iou: Sequence[float] = (0.3, 0.5, 0.7), kinds: Sequence[str] = KINDS,
                  recall_points: int = 40, min_score: float = 0.0, roi: Any = _DEFAULT, initial_capacity: int = 1 << 16,
-                 groups: Any = None, mappings: Optional[Dict[str, Any]] = None, initial_frame_capacity: int = 1 << 10):
+                 groups: Any = None, mappings: Optional[Dict[str, Any]] = None, initial_frame_capacity: int = 1 << 10,
+                 tp_errors: Any = None):
         """``roi``: [xmin, xmax, ymin, ymax, zmin, zmax] (strict inequalities) or None for no filter; default = the exporter's
         box.  ``initial_capacity``: records the store holds before it first doubles.  ``groups``: None, True (all axes) or a
         list out of "time", "road", "weather" -- one more table per scene-description subset; ``mappings``: the exporter's
         name -> value dicts under "time_zone" / "road_structures" / "weather_conditions" (None = its defaults);
-        ``initial_frame_capacity``: frames the frame store holds before it first doubles."""
+        ``initial_frame_capacity``: frames the frame store holds before it first doubles.  ``tp_errors``: None, True or a dict of
+        at / min_recall / angle_period -- the true-positive errors of one reference combination beside the AP."""
         if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 2 <= num_classes <= 16:
             raise ValueError(f"dataset_ap: num_classes must be 2..16 (background + classes), got {num_classes!r}")
         iou = [iou] if isinstance(iou, (int, float)) and not isinstance(iou, bool) else iou
@@ -173,6 +241,7 @@ class DatasetAP:
         self.iou, self.kinds = [float(t) for t in iou], list(kinds)
         self.combinations = [(k, t) for k in self.kinds for t in self.iou]
         self.initial_capacity = initial_capacity
+        self.tp = _parse_tp_errors(tp_errors, self.combinations, self.kinds, self.iou, recall_points)
         if isinstance(initial_frame_capacity, bool) or not isinstance(initial_frame_capacity, int) or initial_frame_capacity < 1:
             raise ValueError(f"dataset_ap: initial_frame_capacity must be a positive integer, got {initial_frame_capacity!r}")
         self.initial_frame_capacity = initial_frame_capacity
@@ -187,7 +256,7 @@ class DatasetAP:
     @classmethod
     def from_config(cls, config: Dict[str, Any]) -> Optional["DatasetAP"]:
         """``config['evaluate']['dataset_ap']``: true (defaults) or a dict of iou / kinds / recall_points / min_score / roi /
-        groups.  Absent or false -> None.  The class count comes from ``config['model']['head']['num_classes']``; with
+        groups / tp_errors.  Absent or false -> None.  The class count comes from ``config['model']['head']['num_classes']``; with
         ``groups`` (true, or a list out of "time", "road", "weather") the group names come from ``config['data']`` the way the
         exporter reads them (time_zone / road_structures / weather_conditions, absent = its defaults)."""
         spec = config.get("evaluate", {}).get("dataset_ap")
@@ -197,9 +266,10 @@ class DatasetAP:
             spec = {}
         if not isinstance(spec, dict):
             raise ValueError(f"evaluate.dataset_ap must be true or a dict, got {spec!r}")
-        unknown = sorted(set(spec) - {"iou", "kinds", "recall_points", "min_score", "roi", "groups"})
+        unknown = sorted(set(spec) - {"iou", "kinds", "recall_points", "min_score", "roi", "groups", "tp_errors"})
         if unknown:
-            raise ValueError(f"evaluate.dataset_ap: unknown key(s) {unknown} (iou, kinds, recall_points, min_score, roi, groups)")
+            raise ValueError(f"evaluate.dataset_ap: unknown key(s) {unknown} (iou, kinds, recall_points, min_score, roi, groups, "
+                             f"tp_errors)")
         try:
             ncls = config["model"]["head"]["num_classes"]
         except (KeyError, TypeError):
@@ -216,6 +286,7 @@ class DatasetAP:
         self._bound = 0                                   # host-known upper bound of the cursor: sum of B * N so far
         self._frames: Optional[torch.Tensor] = None       # groups only: (frame capacity, FRAME_ROW) int32 on the device
         self._nframes = 0                                 # rows of it written so far (host-known and exact: one per frame)
+        self._tp_rows: Optional[torch.Tensor] = None      # tp_errors only: (capacity, 4) int64 on the device, beside the records
 
     def _ensure_frames(self, dev: torch.device, need: int) -> None:
         """Room for ``need`` frame rows, by doubling like the record store."""
@@ -271,6 +342,11 @@ class DatasetAP:
         new = torch.empty((new_cap, 4), dtype=torch.int32, device=dev)
         if self._records is not None and self._bound:
             new[:self._bound].copy_(self._records[:self._bound])
+        if self.tp is not None:                           # the error rows grow with the records: one row per record position
+            rows = torch.empty((new_cap, 4), dtype=torch.int64, device=dev)
+            if self._tp_rows is not None and self._bound:
+                rows[:self._bound].copy_(self._tp_rows[:self._bound])
+            self._tp_rows = rows
         self._records = new
 
     @property
@@ -316,8 +392,9 @@ class DatasetAP:
         args = (cls.data_ptr(), center.data_ptr(), size.data_ptr(), angle.data_ptr(), gt_box.data_ptr(), gt_id.data_ptr(),
                 counts_t.data_ptr(), thr, kinds, K, roi, self.min_score, scratch.data_ptr(), self._records.data_ptr(),
                 self.capacity, self._bound, self._counters.data_ptr(), int(first_frame), B, N, Mmax, ncls)
+        tp = () if self.tp is None else (self._tp_rows.data_ptr(), self.tp["k"], int(self.tp["angle_period"] == "pi"))
         if not self.axes:
-            lib.call("dpft_dataset_ap_update_f32", *args, stream())
+            lib.call("dpft_dataset_ap_update_tp_f32" if tp else "dpft_dataset_ap_update_f32", *args, *tp, stream())
         else:
             ptrs, types, host, _keep = self._descriptions(labels, dev)
             self._ensure_frames(dev, self._nframes + B)
@@ -328,19 +405,23 @@ class DatasetAP:
             for s, a in enumerate(self.axes):
                 for i, (v, _) in enumerate(self.axis_tables[a]):
                     vals[s * MAX_AXIS_VALUES + i] = v
-            lib.call("dpft_dataset_ap_update_groups_f32", *args, ptrs, types, host, cols, cnts, vals, n_axes,
-                     self._frames.data_ptr(), self.frame_capacity, self._nframes, stream())
+            lib.call("dpft_dataset_ap_update_groups_tp_f32" if tp else "dpft_dataset_ap_update_groups_f32", *args, ptrs, types,
+                     host, cols, cnts, vals, n_axes, self._frames.data_ptr(), self.frame_capacity, self._nframes, *tp, stream())
             self._nframes += B
         self._bound += B * N
 
     def state(self) -> Dict[str, torch.Tensor]:
         """The raw state: ``records`` (n, 4) int32 = score bits, frame, query | class << 16, TP bits (in arbitrary order) and
         the int64 ``counters`` ([0] = n, [1] dropped_nan, [16 + c] npos of class c).  Reads the cursor (a sync).  With groups
-        also ``frames`` (F, 18) int32 = frame, group bitmask, npos of classes 0..15 of every frame seen (in arbitrary order)."""
+        also ``frames`` (F, 18) int32 = frame, group bitmask, npos of classes 0..15 of every frame seen (in arbitrary order).  With
+        ``tp_errors`` also ``tp_errors`` (n, 4) int64 parallel to ``records`` = ate, aze, ase, aoe of a TP of the reference
+        combination as rint(e * 2^32), zeros otherwise (counters[3] = errors that did not fit)."""
         if self._counters is None:
             st = {"records": torch.empty((0, 4), dtype=torch.int32), "counters": torch.zeros(N_COUNTERS, dtype=torch.int64)}
             if self.axes:
                 st["frames"] = torch.empty((0, FRAME_ROW), dtype=torch.int32)
+            if self.tp is not None:
+                st["tp_errors"] = torch.empty((0, 4), dtype=torch.int64)
             return st
         counters = self._counters.clone()
         host = counters.cpu()
@@ -350,6 +431,8 @@ class DatasetAP:
         if self.axes:
             st["frames"] = self._frames[:self._nframes].clone() if self._frames is not None else \
                 torch.empty((0, FRAME_ROW), dtype=torch.int32, device=counters.device)
+        if self.tp is not None:
+            st["tp_errors"] = self._tp_rows[:int(host[CURSOR])].clone()
         return st
 
     def load_state(self, state: Dict[str, torch.Tensor]) -> None:
@@ -361,6 +444,10 @@ class DatasetAP:
         if self.axes and (frames is None or frames.dim() != 2 or frames.shape[1] != FRAME_ROW or frames.dtype != torch.int32
                           or frames.is_cuda != records.is_cuda):
             raise ValueError(f"DatasetAP.load_state: with groups the state needs 'frames' (F, {FRAME_ROW}) int32 beside the records")
+        rows = state.get("tp_errors") if self.tp is not None else None
+        if self.tp is not None and (rows is None or rows.shape != (records.shape[0], 4) or rows.dtype != torch.int64
+                                    or rows.is_cuda != records.is_cuda):
+            raise ValueError("DatasetAP.load_state: with tp_errors the state needs 'tp_errors' (n, 4) int64 beside the records")
         n = int(records.shape[0])
         self.reset()
         if not records.is_cuda:
@@ -370,6 +457,8 @@ class DatasetAP:
         self._bound = n
         self._ensure(records.device, n)
         self._records[:n].copy_(records)
+        if rows is not None:
+            self._tp_rows[:n].copy_(rows)
         self._counters.copy_(counters)
         self._counters[CURSOR] = n
         if frames is not None:
@@ -378,10 +467,10 @@ class DatasetAP:
             self._nframes = int(frames.shape[0])
 
     def merge(self, other: "DatasetAP") -> None:
-        """Concatenates the record stores (with groups also the frame stores) and adds the counters (the frames of the two must
-        not overlap)."""
-        if (other.combinations, other.num_classes, other.recall_points, other.group_names, other.axis_tables) != \
-                (self.combinations, self.num_classes, self.recall_points, self.group_names, self.axis_tables):
+        """Concatenates the record stores (with groups also the frame stores, with tp_errors also the error rows) and adds the
+        counters (the frames of the two must not overlap)."""
+        if (other.combinations, other.num_classes, other.recall_points, other.group_names, other.axis_tables, other.tp) != \
+                (self.combinations, self.num_classes, self.recall_points, self.group_names, self.axis_tables, self.tp):
             raise ValueError("DatasetAP.merge: the two accumulators differ in their parameters")
         a, b = self.state(), other.state()
         if not b["records"].is_cuda:
@@ -393,11 +482,14 @@ class DatasetAP:
               "counters": a["counters"] + b["counters"].to(a["counters"].device)}
         if self.axes:
             st["frames"] = torch.cat((a["frames"], b["frames"].to(a["frames"].device)))
+        if self.tp is not None:
+            st["tp_errors"] = torch.cat((a["tp_errors"], b["tp_errors"].to(a["tp_errors"].device)))
         self.load_state(st)
 
     def all_gather(self) -> None:
         """Under ``torch.distributed`` with more than one rank: every rank ends up with all ranks' records and the summed
-        counters (``gather_state``; with groups also all ranks' frame rows), so every rank computes the same table.  A no-op
+        counters (``gather_state``; with groups also all ranks' frame rows, with tp_errors the error rows), so every rank computes
+        the same table.  A no-op
         otherwise."""
         import torch.distributed as dist
         if not (dist.is_initialized() and dist.get_world_size() > 1):
@@ -414,6 +506,11 @@ class DatasetAP:
         """(class, score desc, frame asc, query asc): two stable integer sorts (-0 orders as +0)."""
         if records.shape[0] == 0:
             return records
+        return records[DatasetAP.sort_permutation(records)].contiguous()
+
+    @staticmethod
+    def sort_permutation(records: torch.Tensor) -> torch.Tensor:
+        """The permutation ``sort_records`` applies (for the rows that travel beside the records)."""
         bits = records[:, 0].to(torch.int64) & 0xFFFFFFFF
         bits = torch.where(bits == 0x80000000, torch.zeros_like(bits), bits)
         order = torch.where((bits & 0x80000000) != 0, ~bits & 0xFFFFFFFF, bits | 0x80000000)
@@ -421,8 +518,7 @@ class DatasetAP:
         minor = (records[:, 1].to(torch.int64) << 16) | (w2 & 0xFFFF)
         major = (((w2 >> 16) & 0xFF) << 32) | (0xFFFFFFFF - order)
         idx = torch.sort(minor, stable=True).indices
-        idx = idx[torch.sort(major[idx], stable=True).indices]
-        return records[idx].contiguous()
+        return idx[torch.sort(major[idx], stable=True).indices]
 
     def key(self, kind: str, thr: float) -> str:
         return f"{kind}@{thr:g}"
@@ -434,33 +530,51 @@ class DatasetAP:
         ``all``, ``AP_{kind}@{iou}/{c}/{axis}={name}``, ``mAP_{kind}@{iou}/{axis}={name}``, ``npos/{c}/{axis}={name}`` and
         ``nframes/{axis}={name}``, the count ``bad_description``, the fp64 tensors ``group_ap`` (G, C-1, K), ``group_tp``
         (G, C-1, K), ``group_npos`` (G, C-1), ``group_nframes`` (G) and the list ``group_names`` (``all`` first); the keys
-        without a group are then the ``all`` group's."""
+        without a group are then the ``all`` group's.  With ``tp_errors`` also ``ATE/{c}``, ``AZE/{c}``, ``ASE/{c}``,
+        ``AOE/{c}``, ``mATE`` .. ``mAOE``, ``tp_points/{c}`` (with the group suffix of the AP keys), ``tp_saturated`` and the fp64
+        tensors ``tp_err`` (C-1, 4), ``tp_points`` (C-1), with groups ``group_tp_err`` (G, C-1, 4) and ``group_tp_points``
+        (G, C-1); every TP-error value is NaN when ``tp_saturated`` is not zero."""
         from dpft_amd.hip.lib import lib, stream
         Cn, K = self.num_classes, len(self.combinations)
         groups = None
+        tp_err, tp_points = torch.full((Cn - 1, 4), float("nan"), dtype=torch.float64), torch.zeros(Cn - 1, dtype=torch.float64)
+        saturated = 0
         if self.axes:
             groups = self._compute_groups()
             ap, tp, npos, dropped = groups["group_ap"][0], groups["group_tp"][0], groups["group_npos"][0], groups.pop("dropped")
+            if self.tp is not None:
+                tp_err, tp_points, saturated = groups["group_tp_err"][0], groups["group_tp_points"][0], groups.pop("saturated")
         elif self._counters is None:
             ap = torch.full((Cn - 1, K), float("nan"), dtype=torch.float64)
             npos, tp, dropped = torch.zeros(Cn - 1, dtype=torch.float64), torch.zeros((Cn - 1, K), dtype=torch.float64), 0
         else:
             st = self.state()
             dev = st["counters"].device
-            rec = self.sort_records(st["records"])
-            n = int(rec.shape[0])
+            n = int(st["records"].shape[0])
+            perm = self.sort_permutation(st["records"]) if n else None
+            rec = st["records"][perm].contiguous() if n else st["records"]
             cls_of = (rec[:, 2] >> 16) & 0xFF
             start = torch.searchsorted(cls_of.contiguous(), torch.arange(Cn + 1, dtype=cls_of.dtype, device=dev)).to(torch.int64)
             if n == 0:
                 rec = torch.zeros((1, 4), dtype=torch.int32, device=dev)
-            out = torch.empty((Cn - 1) * (2 * K + 1), dtype=torch.float64, device=dev)
+            base = (Cn - 1) * (2 * K + 1)
+            out = torch.empty(base + ((Cn - 1) * 5 if self.tp is not None else 0), dtype=torch.float64, device=dev)
             ap_d, tp_d, npos_d = out[:(Cn - 1) * K], out[(Cn - 1) * K:2 * (Cn - 1) * K], out[2 * (Cn - 1) * K:]
             lib.call("dpft_dataset_ap_finalize_f64", rec.data_ptr(), n, start.data_ptr(), st["counters"].data_ptr(), Cn, K,
                      self.recall_points, ap_d.data_ptr(), npos_d.data_ptr(), tp_d.data_ptr(), stream())
+            if self.tp is not None:      # the error rows by the records' permutation; one more launch, the same read-back
+                rows = st["tp_errors"][perm].contiguous() if n else torch.zeros((1, 4), dtype=torch.int64, device=dev)
+                lib.call("dpft_dataset_ap_finalize_tp_f64", rec.data_ptr(), rows.data_ptr(), n, start.data_ptr(),
+                         st["counters"].data_ptr(), Cn, self.tp["k"], self.recall_points, self.tp["i_min"], out[base:].data_ptr(),
+                         out[base + (Cn - 1) * 4:].data_ptr(), stream())
             host = out.cpu()
             ap, tp = host[:(Cn - 1) * K].reshape(Cn - 1, K), host[(Cn - 1) * K:2 * (Cn - 1) * K].reshape(Cn - 1, K)
-            npos = host[2 * (Cn - 1) * K:]
-            dropped = int(st["counters"][DROPPED_NAN])
+            npos = host[2 * (Cn - 1) * K:base]
+            counters = st["counters"].cpu()
+            dropped = int(counters[DROPPED_NAN])
+            if self.tp is not None:
+                tp_err, tp_points = host[base:base + (Cn - 1) * 4].reshape(Cn - 1, 4), host[base + (Cn - 1) * 4:]
+                saturated = int(counters[TP_SATURATED])
         res: Dict[str, Any] = {}
         for k, (kind, thr) in enumerate(self.combinations):
             name = self.key(kind, thr)
@@ -472,6 +586,12 @@ class DatasetAP:
             res[f"npos/{c}"] = float(npos[c - 1])
         res["dropped_nan"] = float(dropped)
         res["ap"], res["npos"], res["tp"] = ap, npos, tp
+        if self.tp is not None:
+            if saturated:                # an error did not fit the fixed point: no plausible number comes out of its sums
+                tp_err = torch.full_like(tp_err, float("nan"))
+            self._tp_keys(res, tp_err.tolist(), tp_points.tolist(), "")
+            res["tp_saturated"] = float(saturated)
+            res["tp_err"], res["tp_points"] = tp_err, tp_points
         if groups is not None:
             all_ap, all_npos, all_nframes = (groups[k].tolist() for k in ("group_ap", "group_npos", "group_nframes"))
             for g, gname in enumerate(self.group_names[1:], 1):      # (plain lists: ~800 reads of a host tensor cost milliseconds)
@@ -485,10 +605,27 @@ class DatasetAP:
                 for c in range(1, Cn):
                     res[f"npos/{c}/{gname}"] = gnpos[c - 1]
                 res[f"nframes/{gname}"] = all_nframes[g]
+            if self.tp is not None:
+                if saturated:
+                    groups["group_tp_err"] = torch.full_like(groups["group_tp_err"], float("nan"))
+                all_err, all_points = groups["group_tp_err"].tolist(), groups["group_tp_points"].tolist()
+                for g, gname in enumerate(self.group_names[1:], 1):
+                    self._tp_keys(res, all_err[g], all_points[g], "/" + gname)
             res["bad_description"] = float(groups.pop("bad"))
             res.update(groups)
             res["group_names"] = list(self.group_names)
         return res
+
+    def _tp_keys(self, res: Dict[str, Any], err: List[List[float]], points: List[float], tail: str) -> None:
+        """The TP-error scalars of one table (``tail`` = the group suffix): per class, and the mean over the classes that are not
+        NaN."""
+        for e, name in enumerate(TP_ERRORS):
+            vals = [err[c][e] for c in range(self.num_classes - 1) if err[c][e] == err[c][e]]
+            for c in range(1, self.num_classes):
+                res[f"{name}/{c}{tail}"] = err[c - 1][e]
+            res[f"m{name}{tail}"] = sum(vals) / len(vals) if vals else float("nan")
+        for c in range(1, self.num_classes):
+            res[f"tp_points/{c}{tail}"] = points[c - 1]
 
     def _compute_groups(self) -> Dict[str, Any]:
         """The grouped finalize: the records sorted as always, every record's group bitmask looked up in the frame store by its
@@ -497,15 +634,22 @@ class DatasetAP:
         from dpft_amd.hip.lib import lib, stream
         Cn, K, G = self.num_classes, len(self.combinations), len(self.group_names)
         sizes = (G * (Cn - 1) * K, G * (Cn - 1) * K, G * (Cn - 1), G, 1)          # ap, tp, npos, nframes, bad
+        if self.tp is not None:
+            sizes += (G * (Cn - 1) * 4, G * (Cn - 1))                             # tp_err, tp_points
+        saturated = 0
         if self._counters is None:
             host = torch.cat([torch.full((sizes[0],), float("nan"), dtype=torch.float64),
-                              torch.zeros(sum(sizes[1:]), dtype=torch.float64)])
+                              torch.zeros(sum(sizes[1:5]), dtype=torch.float64)])
+            if self.tp is not None:
+                host = torch.cat([host, torch.full((sizes[5],), float("nan"), dtype=torch.float64),
+                                  torch.zeros(sizes[6], dtype=torch.float64)])
             dropped = 0
         else:
             st = self.state()
             dev = st["counters"].device
-            rec = self.sort_records(st["records"])
-            n, F = int(rec.shape[0]), int(st["frames"].shape[0])
+            n, F = int(st["records"].shape[0]), int(st["frames"].shape[0])
+            perm = self.sort_permutation(st["records"]) if n else None
+            rec = st["records"][perm].contiguous() if n else st["records"]
             cls_of = (rec[:, 2] >> 16) & 0xFF
             start = torch.searchsorted(cls_of.contiguous(), torch.arange(Cn + 1, dtype=cls_of.dtype, device=dev)).to(torch.int64)
             if n and F:
@@ -524,15 +668,25 @@ class DatasetAP:
                 masks[s] = ((1 << len(self.axis_tables[a])) - 1) << bit
                 bit += len(self.axis_tables[a])
             out = torch.empty(sum(sizes), dtype=torch.float64, device=dev)
-            o = [sum(sizes[:i]) for i in range(5)]
+            o = [sum(sizes[:i]) for i in range(len(sizes))]
             lib.call("dpft_dataset_ap_finalize_groups_f64", rec.data_ptr(), rec_groups.data_ptr(), n, start.data_ptr(),
                      frames.data_ptr(), F, masks, len(self.axes), G, Cn, K, self.recall_points, out[o[0]:].data_ptr(),
                      out[o[2]:].data_ptr(), out[o[1]:].data_ptr(), out[o[3]:].data_ptr(), out[o[4]:].data_ptr(), stream())
+            if self.tp is not None:      # after the launches above on the same stream: it reads the npos they wrote
+                rows = st["tp_errors"][perm].contiguous() if n else torch.zeros((1, 4), dtype=torch.int64, device=dev)
+                lib.call("dpft_dataset_ap_finalize_tp_groups_f64", rec.data_ptr(), rows.data_ptr(), rec_groups.data_ptr(), n,
+                         start.data_ptr(), out[o[2]:].data_ptr(), G, Cn, self.tp["k"], self.recall_points, self.tp["i_min"],
+                         out[o[5]:].data_ptr(), out[o[6]:].data_ptr(), stream())
             host = out.cpu()
-            dropped = int(st["counters"][DROPPED_NAN])
-        ap, tp, npos, nframes, bad = torch.split(host, sizes)
-        return {"group_ap": ap.reshape(G, Cn - 1, K), "group_tp": tp.reshape(G, Cn - 1, K), "group_npos": npos.reshape(G, Cn - 1),
-                "group_nframes": nframes.clone(), "bad": int(bad[0]), "dropped": dropped}
+            counters = st["counters"].cpu()
+            dropped, saturated = int(counters[DROPPED_NAN]), int(counters[TP_SATURATED])
+        ap, tp, npos, nframes, bad = torch.split(host, sizes)[:5]
+        res = {"group_ap": ap.reshape(G, Cn - 1, K), "group_tp": tp.reshape(G, Cn - 1, K), "group_npos": npos.reshape(G, Cn - 1),
+               "group_nframes": nframes.clone(), "bad": int(bad[0]), "dropped": dropped}
+        if self.tp is not None:
+            err, points = torch.split(host, sizes)[5:]
+            res.update(group_tp_err=err.reshape(G, Cn - 1, 4), group_tp_points=points.reshape(G, Cn - 1), saturated=saturated)
+        return res
 
     def scalars(self) -> Dict[str, float]:
         """``compute()`` without the tensors: what the evaluation loops return and log."""

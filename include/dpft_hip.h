@@ -1007,6 +1007,49 @@ int dpft_dataset_ap_finalize_groups_f64(const void* records_sorted, const uint32
                                         double* bad, dpft_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * True-positive errors beside the split-level AP (evaluate.dataset_ap.tp_errors; dpft_amd/evaluation/dataset_ap.py
+ * states the definition).  ref_k < K is the reference combination; a TP of it is the (detection, target) pair the greedy
+ * walk of dpft_dataset_ap_update_f32 makes for that combination.
+ * update_tp / update_groups_tp: dpft_dataset_ap_update_f32 / _groups_f32 (same two launches, the same records, counters
+ *   and frame rows) whose match pass also writes row `position of the record` of tp_errors (capacity rows of 4 int64,
+ *   16-byte aligned, the capacity of `records`): for a TP of ref_k the errors ate = sqrt(dx^2 + dy^2), aze = |dz|,
+ *   ase = 1 - P / (Vd + Vg - P) with P = min(l) min(w) min(h), aoe = atan2(|s1 c2 - c1 s2|, c1 c2 + s1 s2) on the
+ *   hypot-normalised (sin, cos) pairs (fold_pi = 1: min(aoe, pi - aoe)), each in fp64 from the fp32 inputs and stored as
+ *   rint(e * 2^32), half to even; zeros for every other record.  An error that is not finite or not below 2^20 in
+ *   magnitude stores 2^52 and counts in counters[3].  The kernel never writes at or past capacity.
+ * finalize_tp: tp_errors_sorted (n_records x 4 int64, 16-byte aligned) = the error rows in the order of records_sorted.
+ *   One workgroup per class: T = running TP count of ref_k, S = running integer sums; the TP with count T serves the
+ *   recall points floor((T-1) R / npos) < i <= min(floor(T R / npos), R) with S / 2^32 / T; tp_err (C-1,4) = mean of the
+ *   served points i >= i_min (1 <= i_min <= R) in ascending i, NaN when none is served; tp_points (C-1) their count.
+ * finalize_tp_groups: the same per (group, class) over the member records (record_groups as finalize_groups takes it),
+ *   group_npos (G,C-1, device) = the npos finalize_groups wrote; tp_err (G,C-1,4), tp_points (G,C-1): the bits of an
+ *   ungrouped run over the group's frames.  All outputs fp64.
+ * ---------------------------------------------------------------------------------------- */
+int dpft_dataset_ap_update_tp_f32(const float* cls, const float* center, const float* size, const float* angle,
+                                  const float* gt_box, const int32_t* gt_id, const int32_t* counts,
+                                  const double* iou_thrs, const int32_t* kinds, int32_t K, const float* roi6,
+                                  float min_score, void* scratch, void* records, int64_t capacity, int64_t reserved,
+                                  int64_t* counters, int32_t first_frame, int32_t B, int32_t N, int32_t Mmax,
+                                  int32_t C, void* tp_errors, int32_t ref_k, int32_t fold_pi, dpft_stream_t stream);
+int dpft_dataset_ap_update_groups_tp_f32(const float* cls, const float* center, const float* size, const float* angle,
+                                         const float* gt_box, const int32_t* gt_id, const int32_t* counts,
+                                         const double* iou_thrs, const int32_t* kinds, int32_t K, const float* roi6,
+                                         float min_score, void* scratch, void* records, int64_t capacity,
+                                         int64_t reserved, int64_t* counters, int32_t first_frame, int32_t B, int32_t N,
+                                         int32_t Mmax, int32_t C, const void* const* desc_ptrs, const int32_t* desc_types,
+                                         const double* desc_host, const int32_t* axis_cols, const int32_t* axis_counts,
+                                         const int32_t* axis_values, int32_t n_axes, void* frames, int64_t frame_capacity,
+                                         int64_t frames_before, void* tp_errors, int32_t ref_k, int32_t fold_pi,
+                                         dpft_stream_t stream);
+int dpft_dataset_ap_finalize_tp_f64(const void* records_sorted, const int64_t* tp_errors_sorted, int64_t n_records,
+                                    const int64_t* class_start, const int64_t* counters, int32_t C, int32_t ref_k,
+                                    int32_t R, int32_t i_min, double* tp_err, double* tp_points, dpft_stream_t stream);
+int dpft_dataset_ap_finalize_tp_groups_f64(const void* records_sorted, const int64_t* tp_errors_sorted,
+                                           const uint32_t* record_groups, int64_t n_records, const int64_t* class_start,
+                                           const double* group_npos, int32_t G, int32_t C, int32_t ref_k, int32_t R,
+                                           int32_t i_min, double* tp_err, double* tp_points, dpft_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Rotated-box NMS between the model and its consumers (dpft_amd/evaluation/nms.py states the definition; the reference
  * has no such step).  Three launches on `stream`, no read-back, no floating-point atomics: the same input gives the
  * same bits.  Per sample: candidates = queries with argmax class c != 0 (first maximum, NaN = maximum) and a non-NaN

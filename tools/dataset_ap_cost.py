@@ -13,8 +13,16 @@ ungrouped one of the same process:
 4. ``DatasetAP.compute()`` on about 2 * 10^5 records with 19 groups beside the ungrouped ``compute()`` on the same records, and
    the two finalize entries alone between device events.
 
-Prints JSON lines and writes them to ``--out`` (default profiles/dataset_ap.txt, with ``--groups`` profiles/dataset_ap_groups.txt).
-Usage: python tools/dataset_ap_cost.py [--groups] [--reps 200] [--records 200000] [--out FILE]"""
+With ``--tp-errors`` the true-positive errors' leg instead (evaluate.dataset_ap.tp_errors), every figure beside the run without the
+key in the same process:
+
+5. ``DatasetAP.update`` with and without the key on the same tensors, measured twice each (a, b, a, b): the two figures of one
+   side show the run-to-run spread that a difference has to exceed; and the update entries alone on pre-packed targets.
+6. ``DatasetAP.compute()`` on about 2 * 10^5 records with and without the key, and the two finalize entries alone.
+
+Prints JSON lines and writes them to ``--out`` (default profiles/dataset_ap.txt, with ``--groups`` profiles/dataset_ap_groups.txt,
+with ``--tp-errors`` profiles/dataset_ap_tp.txt).
+Usage: python tools/dataset_ap_cost.py [--groups | --tp-errors] [--reps 200] [--records 200000] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -33,10 +41,14 @@ def main():
     p.add_argument("--reps", type=int, default=200)
     p.add_argument("--records", type=int, default=200000)
     p.add_argument("--groups", action="store_true", help="the groups leg (3., 4.) instead of 1. and 2.")
+    p.add_argument("--tp-errors", action="store_true", help="the true-positive errors' leg (5., 6.) instead of 1. and 2.")
     p.add_argument("--out", default=None)
     args = p.parse_args()
+    if args.groups and args.tp_errors:
+        p.error("--groups and --tp-errors are separate legs")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "dataset_ap_groups.txt" if args.groups else "dataset_ap.txt")
+        name = "dataset_ap_groups.txt" if args.groups else "dataset_ap_tp.txt" if args.tp_errors else "dataset_ap.txt"
+        args.out = os.path.join(ROOT, "profiles", name)
     import numpy as np
     import torch
     import dataset_ap_ref as R                                  # the tests' seeded sample builder
@@ -76,6 +88,12 @@ def main():
 
     if args.groups:
         groups_leg(args, torch, DatasetAP, lib, stream, dev, out, labels, B, N, Cn, timed, emit)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
+
+    if args.tp_errors:
+        tp_leg(args, torch, DatasetAP, KINDS, pack_targets, lib, stream, dev, out, labels, B, N, Cn, timed, emit)
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")
         return
@@ -221,6 +239,106 @@ def groups_leg(args, torch, DatasetAP, lib, stream, dev, out, labels, B, N, Cn, 
           "dpft_dataset_ap_finalize_f64 alone": timed(finalize_plain),
           "dpft_dataset_ap_finalize_groups_f64 alone (one workgroup per group, class, combination)": timed(finalize_groups),
           "mAP_3d@0.5/weather=fog": res["mAP_3d@0.5/weather=fog"]})
+
+
+def tp_leg(args, torch, DatasetAP, KINDS, pack_targets, lib, stream, dev, out, labels, B, N, Cn, timed, emit):
+    """5. and 6. of the module docstring: an accumulator with the key and one without, fed the same batches in the same process."""
+    plain, tp = DatasetAP(Cn, initial_capacity=1 << 22), DatasetAP(Cn, initial_capacity=1 << 22, tp_errors=True)
+    frame = {"plain": 0, "tp": 0}
+
+    def update(ap, key):
+        def fn():
+            ap.update(out, labels, frame[key])
+            frame[key] += B
+        return fn
+
+    plain.update(out, labels, 0)
+    n_det = int(plain.state()["counters"][0])
+    n_tp = int(((plain.state()["records"][:, 3] >> tp.tp["k"]) & 1).sum())
+    plain.reset()
+    t_plain, t_tp = [], []
+    for _ in range(2):                                          # a, b, a, b: the spread of one side beside the difference
+        t_plain.append(timed(update(plain, "plain")))
+        t_tp.append(timed(update(tp, "tp")))
+
+    # the entries alone, on pre-packed targets
+    counts = [int(l["gt_class"].shape[0]) for l in labels]
+    gt_box, _, gt_id, counts_t, Mmax = pack_targets(labels, counts, Cn, dev)
+    K = len(plain.combinations)
+    thr = (C.c_double * K)(*[t for _, t in plain.combinations])
+    kinds = (C.c_int32 * K)(*[KINDS.index(k) for k, _ in plain.combinations])
+    roi = (C.c_float * 6)(*plain.roi)
+    scratch = torch.empty(int(lib.dpft_dataset_ap_scratch_bytes(B, N, Mmax)) // 8, dtype=torch.float64, device=dev)
+    records = torch.empty((1 << 22, 4), dtype=torch.int32, device=dev)
+    rows = torch.empty((1 << 22, 4), dtype=torch.int64, device=dev)
+    counters = torch.zeros(32, dtype=torch.int64, device=dev)
+    reserved = [0]
+    t4 = [out[k].contiguous() for k in ("class", "center", "size", "angle")]
+
+    def entry(name, *extra):
+        def fn():
+            if reserved[0] + B * N > records.shape[0]:
+                reserved[0] = 0
+                counters.zero_()
+            lib.call(name, *[t.data_ptr() for t in t4], gt_box.data_ptr(), gt_id.data_ptr(), counts_t.data_ptr(), thr, kinds, K, roi,
+                     0.0, scratch.data_ptr(), records.data_ptr(), records.shape[0], reserved[0], counters.data_ptr(), 0, B, N, Mmax,
+                     Cn, *extra, stream())
+            reserved[0] += B * N
+        return fn
+
+    e_plain, e_tp = [], []
+    for _ in range(2):
+        e_plain.append(timed(entry("dpft_dataset_ap_update_f32")))
+        e_tp.append(timed(entry("dpft_dataset_ap_update_tp_f32", rows.data_ptr(), tp.tp["k"], 0)))
+    emit({"what": "update with and without tp_errors, between device events, each side measured twice (a, b, a, b)",
+          "device": torch.cuda.get_device_name(0), "B": B, "N": N, "C": Cn, "targets": counts, "K": K, "at": list(tp.tp["at"]),
+          "detections_per_update": n_det, "tps_per_update": n_tp, "reps": args.reps,
+          "DatasetAP.update without tp_errors": t_plain, "DatasetAP.update with tp_errors": t_tp,
+          "dpft_dataset_ap_update_f32 alone": e_plain, "dpft_dataset_ap_update_tp_f32 alone": e_tp})
+
+    # compute() on ~ --records records: the same batch under new frame numbers
+    plain.reset()
+    tp.reset()
+    first = 0
+    while plain._bound < args.records * N // max(n_det // B, 1):
+        plain.update(out, labels, first)
+        tp.update(out, labels, first)
+        first += B
+    torch.cuda.synchronize()
+    walls = {"plain": [], "tp": []}
+    for _ in range(5):
+        for key, ap in (("plain", plain), ("tp", tp)):
+            t0 = time.perf_counter()
+            res = ap.compute()
+            walls[key].append((time.perf_counter() - t0) * 1e3)
+    assert torch.equal(res["ap"].view(torch.int64), plain.compute()["ap"].view(torch.int64))
+
+    # the finalize entries alone, on the sorted records
+    st = tp.state()
+    perm = DatasetAP.sort_permutation(st["records"])
+    rec, srows = st["records"][perm].contiguous(), st["tp_errors"][perm].contiguous()
+    n = int(rec.shape[0])
+    cls_of = (rec[:, 2] >> 16) & 0xFF
+    start = torch.searchsorted(cls_of.contiguous(), torch.arange(Cn + 1, dtype=cls_of.dtype, device=dev)).to(torch.int64)
+    buf = torch.empty((Cn - 1) * (2 * K + 1 + 5), dtype=torch.float64, device=dev)
+    o = [0, (Cn - 1) * K, 2 * (Cn - 1) * K, (Cn - 1) * (2 * K + 1), (Cn - 1) * (2 * K + 5)]
+
+    def finalize_plain():
+        lib.call("dpft_dataset_ap_finalize_f64", rec.data_ptr(), n, start.data_ptr(), st["counters"].data_ptr(), Cn, K, 40,
+                 buf[o[0]:].data_ptr(), buf[o[2]:].data_ptr(), buf[o[1]:].data_ptr(), stream())
+
+    def finalize_tp():
+        lib.call("dpft_dataset_ap_finalize_tp_f64", rec.data_ptr(), srows.data_ptr(), n, start.data_ptr(), st["counters"].data_ptr(),
+                 Cn, tp.tp["k"], 40, tp.tp["i_min"], buf[o[3]:].data_ptr(), buf[o[4]:].data_ptr(), stream())
+
+    emit({"what": "compute() wall clock, ms, with tp_errors beside the compute() without on the same records", "records": n,
+          "compute_ms_median without tp_errors": round(statistics.median(walls["plain"]), 2),
+          "compute_ms_median with tp_errors": round(statistics.median(walls["tp"]), 2),
+          "compute_ms_min without tp_errors": round(min(walls["plain"]), 2), "compute_ms_min with tp_errors": round(min(walls["tp"]), 2),
+          "dpft_dataset_ap_finalize_f64 alone": timed(finalize_plain),
+          "dpft_dataset_ap_finalize_tp_f64 alone (one workgroup per class)": timed(finalize_tp),
+          "gather of the error rows by the sort permutation": timed(lambda: st["tp_errors"][perm].contiguous()),
+          "mATE": res["mATE"], "mAZE": res["mAZE"], "mASE": res["mASE"], "mAOE": res["mAOE"], "tp_saturated": res["tp_saturated"]})
 
 
 if __name__ == "__main__":
