@@ -1215,6 +1215,26 @@ int dpft::bn_finalize_sums_batch(const BnSumsBatch& batch, dpft_stream_t stream)
     return check_launch("bn_finalize (column sums, batched)");
 }
 
+// C-ABI face of bn_finalize_sums_batch: the layers as arrays, 1 / M as the launch plan passes it
+extern "C" int dpft_bn_finalize_sums_f32(int32_t n, const uint64_t* const* sums, const float* const* gamma, const float* const* beta,
+                                         float* const* running_mean, float* const* running_var, float* const* bnp, const int64_t* M,
+                                         const int32_t* K, float eps, float momentum, dpft_stream_t stream) {
+    DPFT_REQUIRE(n >= 1 && n <= BnSumsBatch::MAX, "bn_finalize (column sums): 1..%d layers per launch (n=%d)", BnSumsBatch::MAX, n);
+    DPFT_REQUIRE(sums && gamma && beta && bnp && M && K, "bn_finalize (column sums): null array");
+    BnSumsBatch batch;
+    batch.n = n; batch.eps = eps; batch.momentum = momentum;
+    for (int i = 0; i < n; ++i) {
+        DPFT_REQUIRE(sums[i] && gamma[i] && beta[i] && bnp[i] && M[i] > 0 && K[i] > 0, "bn_finalize (column sums): bad layer %d", i);
+        const bool rm = running_mean && running_mean[i], rv = running_var && running_var[i];
+        DPFT_REQUIRE(rm == rv, "bn_finalize (column sums): running stats must come in pairs (layer %d)", i);
+        batch.sums[i] = (const unsigned long long*)sums[i];
+        batch.gamma[i] = gamma[i]; batch.beta[i] = beta[i]; batch.out[i] = bnp[i];
+        batch.rm[i] = rm ? running_mean[i] : nullptr; batch.rv[i] = rv ? running_var[i] : nullptr;
+        batch.invn[i] = 1.0 / (double)M[i]; batch.M[i] = M[i]; batch.K[i] = K[i];
+    }
+    return dpft::bn_finalize_sums_batch(batch, stream);
+}
+
 extern "C" int dpft_bn_act_f32(const float* y, const float* bnp, const float* res, const float* res_bnp,
                                int32_t relu, float* out, int64_t M, int32_t K, dpft_stream_t stream) {
     return dpft::bn_act_any(y, bnp, res, res_bnp, relu, out, nullptr, M, K, false, stream);

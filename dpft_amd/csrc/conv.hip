@@ -1595,6 +1595,24 @@ int dpft::conv_fwd_sums(const dpft_conv_desc* d, const float* x, const float* w,
     return dpft_bn_stats_f32(y, stats, a.M, a.N, p.bm, stream);      // stats from the reduced output (p.bm rows per tile)
 }
 
+// C-ABI face of conv_fwd_sums (the launch plan's forward conv with its statistics / prologue as column sums): no arithmetic here
+extern "C" int dpft_conv2d_nhwc_fwd_sums_f32(const dpft_conv_desc* d, const float* x, const float* w, const float* bias,
+                                             const float* pro_bn, int32_t pro_relu, float* y, float* stats, uint64_t* sums,
+                                             int32_t* sums_used, const uint64_t* pro_sums, const float* pro_gamma,
+                                             const float* pro_beta, int64_t pro_rows, float pro_eps, int32_t* pro_sums_used,
+                                             void* workspace, dpft_stream_t stream) {
+    if (sums_used) *sums_used = 0;
+    if (pro_sums_used) *pro_sums_used = 0;
+    DPFT_REQUIRE(!pro_sums || (pro_gamma && pro_beta && pro_rows > 0 && pro_eps >= 0.f), "conv fwd (column sums): prologue sums without gamma / beta / rows / eps");
+    const dpft::BnSumsRef ps{(const unsigned long long*)pro_sums, pro_gamma, pro_beta, pro_sums ? 1.0 / (double)pro_rows : 0.0, pro_eps, d ? d->C : 0};
+    bool su = false, pu = false;
+    const int rc = dpft::conv_fwd_sums(d, x, w, bias, pro_bn, pro_relu, y, stats, workspace, stream, (unsigned long long*)sums,
+                                       sums_used ? &su : nullptr, pro_sums ? &ps : nullptr, pro_sums_used ? &pu : nullptr);
+    if (sums_used) *sums_used = su ? 1 : 0;
+    if (pro_sums_used) *pro_sums_used = pu ? 1 : 0;
+    return rc;
+}
+
 // Inference form of conv + BatchNorm (+ residual) (+ ReLU): y = [relu](bn(conv(x, w)) [+ residual]) with the BN block of the
 // OUTPUT channels.  One launch when the problem takes the vector path without split-K (the epilogue does it) or with the
 // in-launch fix-up; otherwise the plain convolution followed by the elementwise pass -- same arithmetic, same result.

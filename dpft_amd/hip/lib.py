@@ -153,6 +153,9 @@ SIGNATURES = {
     "dpft_add_inplace_f32": (_I, [_P, _P, _L, _P]),
     "dpft_bn_act_any_f32": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _L, _I, _I, _P]),
     "dpft_bn_act_sums_f32": (_I, [_P] * 10 + [_F, _I, _P, _P, _L, _I, C.POINTER(_I), _P]),
+    "dpft_conv2d_nhwc_fwd_sums_f32": (_I, [_DESC, _P, _P, _P, _P, _I, _P, _P, _P, C.POINTER(_I), _P, _P, _P, _L, _F,
+                                           C.POINTER(_I), _P, _P]),
+    "dpft_bn_finalize_sums_f32": (_I, [_I] + [_P] * 8 + [_F, _F, _P]),
     "dpft_bn_bwd_reduce_any_f32": (_I, [_P] * 7 + [_L, _I, _I, _P]),
     "dpft_bn_bwd_apply_any_f32": (_I, [_P] * 12 + [_I, _L, _I, _I, _I, _P]),
     "dpft_bn_relu_maxpool_any_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),

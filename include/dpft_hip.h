@@ -245,6 +245,23 @@ int dpft_bn_act_sums_f32(const float* y, const float* bnp, const uint64_t* y_sum
                          const float* res, const float* res_bnp, const uint64_t* res_sums, const float* res_gamma,
                          const float* res_beta, float eps, int32_t relu, float* out, uint8_t* mask8, int64_t M,
                          int32_t K, int32_t* used, dpft_stream_t stream);
+/* dpft_conv2d_nhwc_fwd_f32 with the train-mode statistics as column sums (the accumulators described above), one launch:
+ *   sums           [4][K] words (may be NULL; needs `stats` and `sums_used`), zero before the first launch that adds to them.
+ *                  *sums_used = 1: the launch added n * mean and M2 + n * mean^2 of every statistics tile to them INSTEAD of
+ *                  writing `stats`; 0: they are untouched and `stats` holds the per-tile table (a bias, the generic kernel, a
+ *                  K split finished by a reduction launch, K % 4 != 0).
+ *   pro_sums       (may be NULL) the prologue's BatchNorm as column sums [4][C] of the producer over its pro_rows rows, with
+ *                  its gamma / beta / eps; `pro_bn` must still be given.  DPFT_ERR_ARG where the kernel of this conv builds no
+ *                  prologue from sums; *pro_sums_used = 1 where it did. */
+int dpft_conv2d_nhwc_fwd_sums_f32(const dpft_conv_desc* d, const float* x, const float* w, const float* bias,
+                                  const float* pro_bn, int32_t pro_relu, float* y, float* stats, uint64_t* sums,
+                                  int32_t* sums_used, const uint64_t* pro_sums, const float* pro_gamma, const float* pro_beta,
+                                  int64_t pro_rows, float pro_eps, int32_t* pro_sums_used, void* workspace, dpft_stream_t stream);
+/* column sums -> BN block bnp[i][4][K[i]] and running statistics (momentum; unbiased variance; running_mean / running_var or
+ * their entries may be NULL) of n layers in one launch, sums[i] over M[i] rows.  1 <= n <= 48: DPFT_ERR_ARG otherwise. */
+int dpft_bn_finalize_sums_f32(int32_t n, const uint64_t* const* sums, const float* const* gamma, const float* const* beta,
+                              float* const* running_mean, float* const* running_var, float* const* bnp, const int64_t* M,
+                              const int32_t* K, float eps, float momentum, dpft_stream_t stream);
 /* pass 1 (sums [2][K] cleared by the entry) */
 int dpft_bn_bwd_reduce_any_f32(const void* y, const void* dout, const void* out, const float* mask_bnp, const uint8_t* mask8,
                                const float* bnp, float* sums, int64_t M, int32_t K, int32_t storage, dpft_stream_t stream);
