@@ -4,6 +4,7 @@ from dpft_amd.data.loader import (BlockShardedSampler, PrefetchLoader, ShardedSa
                                   load_listed_eval)
 from dpft_amd.data.preprocess import GpuPreprocessor, resized_output_size                        # noqa: F401
 from dpft_amd.data.augment import AugmentSampler, parse_augment                                  # noqa: F401
+from dpft_amd.data.corrupt import CorruptSampler, parse_corrupt                                  # noqa: F401
 from dpft_amd.data.synthetic_raw import SyntheticRawDataset                                      # noqa: F401
 from dpft_amd.data.radar_projection import doppler_raster, radar_projection                      # noqa: F401
 from dpft_amd.data.kradar import KRadarFolderDataset, initialize_kradar                       # noqa: F401

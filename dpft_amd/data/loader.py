@@ -235,7 +235,7 @@ class PrefetchLoader:
                 reuse = max(1, self.slots.per_worker - 2) * self.slots.n_workers
             it, i = iter(self.source), -1
             augments = getattr(self.preprocessor, "augments", False)
-            if augments:                                        # the draws of an epoch follow the sampler's epoch
+            if augments or getattr(self.preprocessor, "corrupts", False):      # the draws of an epoch follow the sampler's epoch
                 self.preprocessor.set_epoch(getattr(self.sampler, "epoch", 0))
             while True:
                 i += 1
@@ -340,6 +340,9 @@ def load_listed_eval(dataset: Dataset, config: Dict[str, Any], device="cpu", ran
     if getattr(preprocessor, "augments", False):
         raise ValueError("load_listed_eval: the training augmentation never runs in evaluation; build the preprocessor with "
                          "GpuPreprocessor.from_config(config) (augment left False)")
+    if getattr(preprocessor, "corrupts", False):
+        raise ValueError("load_listed_eval: train.corrupt never runs in evaluation (evaluate.robustness is the evaluator's own "
+                         "key); build the preprocessor with GpuPreprocessor.from_config(config) (augment left False)")
     sampler = BlockShardedSampler(len(dataset), rank, world)
     workers = config.get("computing", {}).get("workers", 0)
     dl = DataLoader(dataset, batch_size=config["train"]["batch_size"], sampler=sampler, num_workers=workers,

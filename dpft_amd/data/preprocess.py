@@ -62,41 +62,79 @@ def scale_clip(x: torch.Tensor, in_lo: float = MIN_POWER, in_hi: float = MAX_POW
 class GpuPreprocessor:
     """``augment``: None / False (off: the plain transforms, exactly), or a ``train.augment`` value / an
     ``AugmentSampler`` -- the training augmentation of dpft_amd/data/augment.py.  An augmenting preprocessor is called with
-    the labels, ``pre(batch, labels) -> (batch, labels)``: the flip moves frames, radar maps, matrices and labels together."""
+    the labels, ``pre(batch, labels) -> (batch, labels)``: the flip moves frames, radar maps, matrices and labels together.
+    ``corrupt``: None / False (off), or a ``train.corrupt`` value / a ``CorruptSampler`` -- the sensor degradation of
+    dpft_amd/data/corrupt.py, run AFTER the plain or the augmented transforms on their outputs; labels and matrices pass
+    through untouched, so the call keeps the form the ``augment`` setting gives it."""
 
     def __init__(self, image_size: Union[int, Sequence[int], None] = 512, scale: bool = True,
                  camera_keys: Sequence[str] = ("camera_mono", "camera_stereo"),
-                 radar_keys: Sequence[str] = ("radar_bev", "radar_front"), augment=None, seed: int = 0, rank: int = 0):
+                 radar_keys: Sequence[str] = ("radar_bev", "radar_front"), augment=None, seed: int = 0, rank: int = 0,
+                 corrupt=None):
         self.image_size, self.scale = image_size, scale
         self.camera_keys, self.radar_keys = tuple(camera_keys), tuple(radar_keys)
         self.sampler = None
         if augment is not None and augment is not False:
             from dpft_amd.data.augment import AugmentSampler, parse_augment
             self.sampler = augment if isinstance(augment, AugmentSampler) else AugmentSampler(parse_augment(augment), seed, rank)
+        self.corruptor = None
+        if corrupt is not None and corrupt is not False:
+            from dpft_amd.data.corrupt import CorruptSampler, parse_corrupt
+            self.corruptor = corrupt if isinstance(corrupt, CorruptSampler) else CorruptSampler(parse_corrupt(corrupt), seed, rank)
 
     @property
     def augments(self) -> bool:
         return self.sampler is not None
 
+    @property
+    def corrupts(self) -> bool:
+        return self.corruptor is not None
+
     def set_epoch(self, epoch: int) -> None:
         if self.sampler is not None:
             self.sampler.set_epoch(epoch)
+        if self.corruptor is not None:
+            self.corruptor.set_epoch(epoch)
 
     @classmethod
     def from_config(cls, config: Dict, augment: bool = False, rank: int = 0) -> "GpuPreprocessor":
-        """``augment=True`` (the TRAINING loader only): take ``train.augment`` of the config, if it has the key."""
+        """``augment=True`` (the TRAINING loader only): take ``train.augment`` and ``train.corrupt`` of the config, where it has
+        the keys.  Validation and evaluation preprocessors (``augment`` left False) take neither."""
         d = config.get("data", {})
-        spec, seed = None, 0
+        spec, seed, corrupt = None, 0, None
+        if augment and "corrupt" in config.get("train", {}):
+            from dpft_amd.data.corrupt import parse_corrupt
+            corrupt = parse_corrupt(config["train"]["corrupt"])
+            seed = config.get("computing", {}).get("seed", 0)
         if augment and "augment" in config.get("train", {}):
             from dpft_amd.data.augment import check_fov_symmetric, parse_augment
             spec = parse_augment(config["train"]["augment"])
             check_fov_symmetric(spec, d.get("fov"))
             seed = config.get("computing", {}).get("seed", 0)
-        return cls(image_size=d.get("image_size", 512), scale=d.get("scale", True), augment=spec, seed=seed, rank=rank)
+        return cls(image_size=d.get("image_size", 512), scale=d.get("scale", True), augment=spec, seed=seed, rank=rank,
+                   corrupt=corrupt)
+
+    def _corrupted(self, out: Dict[str, torch.Tensor], params=None) -> Dict[str, torch.Tensor]:
+        """The degradation launches on the transforms' outputs.  ``params`` (a pair of lists, ``CameraCorruption`` and
+        ``RadarCorruption`` per sample) overrides the sampler's draw."""
+        from dpft_amd.data import corrupt as K
+        views = [k for k in self.camera_keys + self.radar_keys if k in out]
+        if not views:
+            return out
+        cams, rads = self.corruptor.draw(out[views[0]].shape[0]) if params is None else params
+        return K.corrupt_batch(out, cams, rads, self.camera_keys, self.radar_keys)
 
     def __call__(self, batch: Dict[str, torch.Tensor], labels=None):
+        if self.corruptor is not None:
+            if self.sampler is not None:
+                out, labels = self._augmented(batch, labels)
+                return self._corrupted(out), labels
+            return self._corrupted(self._plain(batch))
         if self.sampler is not None:
             return self._augmented(batch, labels)
+        return self._plain(batch)
+
+    def _plain(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         out = dict(batch)
         for k in self.radar_keys:
             if k in out and self.scale:

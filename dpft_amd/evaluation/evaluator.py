@@ -14,6 +14,7 @@ batch, every forward followed by a device sync).  ``evaluate_complexity`` (:67-9
 not installed here: the parameter count is logged, FLOPS / MACS are left to ``bench.py``'s algorithmic counts."""
 from __future__ import annotations
 
+import copy
 import os
 import os.path as osp
 import shutil
@@ -59,14 +60,20 @@ class DataParallelEvaluator:
     latency_reps, latency_warmup = 300, 10      # evaluator.py:110,114
 
     def __init__(self, metric: Optional[torch.nn.Module] = None, exporter: Optional[Callable] = None,
-                 device: Optional[torch.device] = None, logging: Optional[str] = None, dataset_ap=None, nms=None):
+                 device: Optional[torch.device] = None, logging: Optional[str] = None, dataset_ap=None, nms=None,
+                 robustness=None):
         """``logging``: None, 'step' or 'epoch' (evaluator.py:24-28).  ``dataset_ap``: an optional
         ``dpft_amd.evaluation.dataset_ap.DatasetAP`` -- split-level AP_BEV / AP_3D accumulated beside the per-step metrics.
         ``nms``: an optional ``dpft_amd.evaluation.nms.RotatedNMS`` -- the metric, the split-level AP and the exporter then read
-        ``nms.suppress(output)`` instead of the model's raw output (not in the reference: its numbers and files differ)."""
+        ``nms.suppress(output)`` instead of the model's raw output (not in the reference: its numbers and files differ).
+        ``robustness``: an optional ``dpft_amd.evaluation.robustness.RobustnessSuite`` -- after a batch's clean pass every
+        condition runs one more forward on the degraded batch and feeds its own metric sums and split-level AP
+        (``{key}/cond={name}``); K conditions cost K extra forwards per batch.  The exporter sees the clean output only."""
         self.eval_fn, self.export_fn, self.logging = metric, exporter, logging
         self.dataset_ap = dataset_ap
         self.nms = nms
+        self.robustness = robustness
+        self.condition_ap: Dict[str, Any] = {}
         self.device = torch.device(device) if device is not None else torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
         self.rank = dist.get_rank() if dist.is_initialized() else 0
         self.world = dist.get_world_size() if dist.is_initialized() else 1
@@ -82,11 +89,15 @@ class DataParallelEvaluator:
         if config.get("evaluate", {}).get("nms"):                 # (absent or false: nothing is imported or built)
             from dpft_amd.evaluation.nms import RotatedNMS
             nms = RotatedNMS.from_config(config)
+        robustness = None
+        if config.get("evaluate", {}).get("robustness"):          # (absent or false: nothing is imported or built)
+            from dpft_amd.evaluation.robustness import RobustnessSuite
+            robustness = RobustnessSuite.from_config(config)
         return cls(metric=build_metric(config["evaluate"]),
                    exporter=build_exporter(config["evaluate"]["exporter"]["name"], config),
                    device=device, logging=config["train"].get("logging"),
                    dataset_ap=DatasetAP.from_config(config),      # (None unless evaluate.dataset_ap is set)
-                   nms=nms)
+                   nms=nms, robustness=robustness)
 
     def __call__(self, *args, **kwargs):
         return self.evaluate(*args, **kwargs)
@@ -112,7 +123,8 @@ class DataParallelEvaluator:
         default to the process group's (tests pass them to play several ranks in one process).  Returns the metric means over
         ALL ranks' steps; with a ``dataset_ap`` also its split-level scalars (``AP_*``, ``mAP_*``, ``npos/*``, ``dropped_nan``),
         which are no step means: they are computed once from all ranks' records (with its ``groups`` also one such table per
-        scene-description subset: ``.../{axis}={name}``, ``nframes/*``, ``bad_description``)."""
+        scene-description subset: ``.../{axis}={name}``, ``nframes/*``, ``bad_description``).  With a ``robustness`` suite every
+        one of these keys comes once more per condition as ``{key}/cond={name}`` (after a group suffix where there is one)."""
         rank = self.rank if rank is None else rank
         world = self.world if world is None else world
         if shard_start is None:
@@ -132,6 +144,9 @@ class DataParallelEvaluator:
         n_steps = len(data_loader) if hasattr(data_loader, "__len__") else 0
         if self.dataset_ap is not None:
             self.dataset_ap.reset()
+        conditions = self.robustness.names if self.robustness is not None else []
+        cond_ap = {name: copy.deepcopy(self.dataset_ap) for name in conditions} if self.dataset_ap is not None else {}
+        self.condition_ap = cond_ap                     # kept for callers that merge several ranks' accumulators themselves
         for i, (data, labels) in enumerate(data_loader):
             labels = [self._dict_to(l) for l in labels]
             data = self._dict_to(data)
@@ -148,6 +163,16 @@ class DataParallelEvaluator:
                 self.dataset_ap.update(output, labels, shard_start + seen)
             if self.export_fn is not None and root is not None:
                 self.export_fn(output, labels, shard_start + seen, root)
+            for name in conditions:                     # one more forward per condition; the clean pass above is untouched
+                out_c = model(self.robustness.apply(name, data, shard_start + seen))
+                if self.nms is not None:
+                    out_c = self.nms.suppress(out_c)
+                for k, v in (self.eval_fn(out_c, labels) if self.eval_fn is not None else {}).items():
+                    k = self.robustness.scalar_key(k, name)
+                    v = torch.as_tensor(v, device=self.device).detach().float().reshape(())
+                    sums[k] = sums[k] + v if k in sums else v.clone()
+                if name in cond_ap:
+                    cond_ap[name].update(out_c, labels, shard_start + seen)
             seen += len(labels)
             steps += 1
         keys = sorted(sums)
@@ -174,6 +199,12 @@ class DataParallelEvaluator:
             if self.logging is not None and rank == 0:
                 self.log_scalars(writer, table, epoch if self.logging == "epoch" else max((epoch + 1) * n_steps - 1, 0), "test")
             scalars.update(table)
+            for name in conditions:                     # one table per condition, from all ranks' records like the clean one
+                cond_ap[name].all_gather()
+                table = {self.robustness.scalar_key(k, name): v for k, v in cond_ap[name].scalars().items()}
+                if self.logging is not None and rank == 0:
+                    self.log_scalars(writer, table, epoch if self.logging == "epoch" else max((epoch + 1) * n_steps - 1, 0), "test")
+                scalars.update(table)
         return scalars
 
     @torch.no_grad()

@@ -114,6 +114,24 @@ class AugmentLabels(C.Structure):
 
 AUGMENT_CHUNK, AUGMENT_MAX_VIEWS = 8, 4      # DPFT_AUGMENT_CHUNK, DPFT_AUGMENT_MAX_VIEWS
 
+CORRUPT_CHUNK, CORRUPT_MAX_RADIUS, CORRUPT_MAX_RECTS, CORRUPT_MAX_BANDS = 8, 15, 4, 4      # DPFT_CORRUPT_*
+
+
+class CorruptCamera(C.Structure):
+    """dpft_corrupt_camera: one sample's camera degradation (include/dpft_hip.h)."""
+    _fields_ = [("key", C.c_uint64), ("view", C.c_int32), ("radius", C.c_int32), ("sigma", C.c_float),
+                ("w", C.c_float * (CORRUPT_MAX_RADIUS + 1)), ("haze", C.c_float), ("airlight", C.c_float * 4),
+                ("noise", C.c_float), ("n_rects", C.c_int32), ("rect", (C.c_int32 * 4) * CORRUPT_MAX_RECTS),
+                ("fill", (C.c_float * 4) * CORRUPT_MAX_RECTS), ("off", C.c_int32)]
+
+
+class CorruptRadar(C.Structure):
+    """dpft_corrupt_radar: one sample's radar degradation (include/dpft_hip.h)."""
+    _fields_ = [("key", C.c_uint64), ("view", C.c_int32), ("noise", C.c_float), ("channels", C.c_uint32),
+                ("n_azimuth", C.c_int32), ("azimuth", (C.c_int32 * 2) * CORRUPT_MAX_BANDS), ("n_rows", C.c_int32),
+                ("rows", (C.c_int32 * 2) * CORRUPT_MAX_BANDS), ("off", C.c_int32), ("pad", C.c_int32)]
+
+
 _P, _I, _L, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 _DESC = C.POINTER(ConvDesc)
 _PYR = C.POINTER(Pyramid)
@@ -217,6 +235,9 @@ SIGNATURES = {
     "dpft_augment_camera_nhwc_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(AugmentSample), _P]),
     "dpft_augment_radar_nhwc_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, C.POINTER(AugmentSample), _P]),
     "dpft_augment_geometry_f32": (_I, [C.POINTER(AugmentView), _I, C.POINTER(AugmentLabels), C.POINTER(AugmentSample), _I, _P]),
+    "dpft_corrupt_limits": (_I, [C.POINTER(_I * 4)]),
+    "dpft_corrupt_camera_nhwc_f32": (_I, [_P, _P, _I, _I, _I, _I, C.POINTER(CorruptCamera), _P]),
+    "dpft_corrupt_radar_nhwc_f32": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, C.POINTER(CorruptRadar), _P]),
     "dpft_detection_metrics_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _P, _P, _I, _I, _I, _I, _P]),
     "dpft_dataset_ap_scratch_bytes": (_L, [_I, _I, _I]),
     "dpft_dataset_ap_update_f32": (_I, [_P] * 9 + [_I, _P, _F, _P, _P, _L, _L, _P, _I, _I, _I, _I, _I, _P]),

@@ -950,6 +950,70 @@ int dpft_augment_geometry_f32(const dpft_augment_view* views, int32_t V, const d
                               const dpft_augment_sample* samples, int32_t B, dpft_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sensor degradation on the device (optional, "train.corrupt" and "evaluate.robustness"; DESIGN.md section 3 "Sensor
+ * degradation").  Both launches work on PREPROCESSED inputs, out of place (dst != src), with the per-sample parameters as a
+ * host array of B samples copied into the kernel arguments, DPFT_CORRUPT_CHUNK samples per launch -- no device copy, no host
+ * wait, no allocation, stream-ordered.  A sample whose parameters are all neutral is copied bit for bit.
+ *
+ * Noise: v + noise * z, product and sum rounded separately, z = float(u0 + u1 + u2 + u3 - 131070) * (1 / 37837.2f) out of four
+ *   16-bit uniforms (Irwin-Hall of order 4: unit variance, |z| < 3.47) that are a pure integer function of (key, view, element
+ *   index within the sample): with mix(x) = the 32-bit multiply-xorshift mixer (x ^= x >> 16, x *= 0x7feb352d, x ^= x >> 15,
+ *   x *= 0x846ca68b, x ^= x >> 16), lo / hi the halves of key,
+ *     s0 = mix(lo ^ mix(hi ^ mix(view ^ 0x9e3779b9))),  s1 = mix(hi ^ mix(lo ^ mix(view ^ 0xc2b2ae35))),
+ *     a = mix(index ^ s0),  b = mix(a ^ s1),  u = the 16-bit halves of a and b.  There is no device random state.
+ *
+ * camera (B,H,W,C <= 4), nominally in [0, 255]; per sample, in this order:
+ *   1. Gaussian blur, separable (horizontal, then vertical), replicate border: radius = ceil(3 sigma) <= DPFT_CORRUPT_MAX_RADIUS
+ *      (sigma in (0, 5]; sigma = 0 and radius = 0: no blur), half table w[0..radius] with w[0] + 2 sum w[k] = 1 (the caller
+ *      normalises exp(-k^2 / 2 sigma^2) in double precision and rounds once).  A tiled LDS kernel: the tile and its halo are staged
+ *      once per workgroup, both passes run out of LDS.
+ *   2. haze: v + haze * (airlight[c] - v), haze in [0, 1], three roundings (haze = 0: skipped);
+ *   3. noise (above), clamped to [0, 255] when noise > 0, index = (y W + x) C + c;
+ *   4. erase: n_rects <= 4 rectangles [x0, x1) x [y0, y1) inside the frame (rect = x0, x1, y0, y1), each set to fill[c];
+ *   5. off: the whole frame becomes 0.
+ * radar (B,H,W,C <= 32), axis 2 = azimuth: noise on the channels of the bit mask `channels`, clamped to [lo, hi] when
+ *   noise > 0; n_azimuth <= 4 bands [a0, a1) of axis 2 and n_rows <= 4 bands [r0, r1) of axis 1 are set to lo; off: 0.
+ * limits (host only): out = tile height, tile width of the camera launch, DPFT_CORRUPT_MAX_RADIUS, DPFT_CORRUPT_CHUNK.
+ * Refused (nothing is launched): sigma outside [0, 5], haze outside [0, 1], NaN or negative noise, C > 4 (camera), a rectangle
+ *   or band outside the frame, weights that do not add up to 1, null pointers, dst == src.
+ * ---------------------------------------------------------------------------------------- */
+#define DPFT_CORRUPT_CHUNK 8
+#define DPFT_CORRUPT_MAX_RADIUS 15
+#define DPFT_CORRUPT_MAX_RECTS 4
+#define DPFT_CORRUPT_MAX_BANDS 4
+typedef struct dpft_corrupt_camera {
+    uint64_t key;
+    int32_t view;
+    int32_t radius;
+    float sigma;
+    float w[DPFT_CORRUPT_MAX_RADIUS + 1];
+    float haze;
+    float airlight[4];
+    float noise;
+    int32_t n_rects;
+    int32_t rect[DPFT_CORRUPT_MAX_RECTS][4];
+    float fill[DPFT_CORRUPT_MAX_RECTS][4];
+    int32_t off;
+} dpft_corrupt_camera;
+typedef struct dpft_corrupt_radar {
+    uint64_t key;
+    int32_t view;
+    float noise;
+    uint32_t channels;
+    int32_t n_azimuth;
+    int32_t azimuth[DPFT_CORRUPT_MAX_BANDS][2];
+    int32_t n_rows;
+    int32_t rows[DPFT_CORRUPT_MAX_BANDS][2];
+    int32_t off;
+    int32_t pad;
+} dpft_corrupt_radar;
+int dpft_corrupt_limits(int32_t out[4]);
+int dpft_corrupt_camera_nhwc_f32(const float* src, float* dst, int32_t B, int32_t H, int32_t W, int32_t C,
+                                 const dpft_corrupt_camera* samples, dpft_stream_t stream);
+int dpft_corrupt_radar_nhwc_f32(const float* x, float* y, int32_t B, int32_t H, int32_t W, int32_t C, float lo, float hi,
+                                const dpft_corrupt_radar* samples, dpft_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-step detection metrics of the reference's train / validation loops (src/dprt/training/trainer.py:134,
  * src/dprt/evaluation/metric.py): mAP3D (IoU threshold, nelem-point "interpolated" curve, :16-151) and mGIoU3D
  * (:154-253) of every sample, on padded targets.  out (B,2) = (mAP, mGIoU) per sample (the caller applies the batch

@@ -10,6 +10,7 @@ the reference: torchvision.io.read_image) and np.load are then inside the worker
     python tools/loader_rate.py            -> one JSON line
     FILES=1 python tools/loader_rate.py    -> the same from files on disk
     AUGMENT=1 python tools/loader_rate.py  -> with "train.augment" set (flip, camera zoom / shift / photometric, radar gain)
+    CORRUPT=1 python tools/loader_rate.py  -> with "train.corrupt" set (blur, haze, noise, erase, masks, off at p = 0.5)
 """
 import copy, json, os, sys, time
 import torch
@@ -69,6 +70,12 @@ def main():
     if augment:
         cfg["train"]["augment"] = {"flip": 0.5, "camera": {"zoom": [0.9, 1.1], "shift": 0.05, "brightness": 0.2, "contrast": 0.2,
                                                             "channel": 0.05}, "radar": {"gain_db": 3.0}}
+    if os.environ.get("CORRUPT") == "1":
+        cfg["train"]["corrupt"] = {"p": 0.5,
+                                   "camera": {"blur": [0, 3], "haze": [0, 0.6], "noise": [0, 20],
+                                              "erase": {"n": [0, 3], "area": [0.02, 0.2], "aspect": [0.3, 3.3]}, "off": 0.05},
+                                   "radar": {"noise": [0, 10], "azimuth_mask": {"n": [0, 2], "width": [1, 12]},
+                                             "range_mask": {"n": [0, 2], "width": [1, 24]}, "off": 0.05}}
     pre = GpuPreprocessor.from_config(cfg, augment=True)
     loader, sampler = load_listed(ds, cfg, device=dev, preprocessor=pre, seed=1)
     it = iter(loader)
@@ -96,6 +103,7 @@ def main():
     torch.cuda.synchronize()
     t_res = (time.perf_counter() - t0) / n
     print(json.dumps({"workers": workers, "steps": n, "batch": B, "augment": cfg["train"].get("augment"),
+                      "corrupt": cfg["train"].get("corrupt"),
                       "loader_in_the_loop_samples_per_s": B / t_loader, "loader_ms_per_step": 1e3 * t_loader,
                       "resident_batch_samples_per_s": B / t_res, "resident_ms_per_step": 1e3 * t_res,
                       "loader_over_resident": t_res / t_loader,
