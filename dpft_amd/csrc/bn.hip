@@ -3,7 +3,7 @@
 // (reference call sites: src/dprt/models/backbones/resnet.py:54-55, src/dprt/models/necks/fpn.py:39-43)
 // and the in-place sinusoidal embedding add (src/dprt/models/embeddings/sinusoidal.py:107-108).
 #include "common.h"
-#include <stdlib.h>
+#include "bn_plan.h"      // the launch plans of the element-wise passes (host only)
 
 #include <algorithm>
 #include <type_traits>
@@ -490,7 +490,7 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_kernel(const float* _
 // channels: (1) relu(bn(y)) of the 11 x 19 pixels its 5 x 9 windows cover goes to LDS once (one load per element + halo),
 // the windows' dout with it; (2) one thread per (window, 4 channels) finds the first arg-max in scan order; (3) one thread
 // per owned element sums the dout of the windows that chose it, in the order of the gather form -- bit-identical results.
-constexpr int PB_TH = 4, PB_TW = 8, PB_CQ = 8;                              // windows owned per tile (rows, cols), channel quads
+// (PB_TH x PB_TW windows owned per tile, PB_CQ channel quads: bn_plan.h)
 constexpr int PB_RH = 2 * PB_TH + 3, PB_RW = 2 * PB_TW + 3;                 // pixels staged
 constexpr int PB_WH = PB_TH + 1, PB_WW = PB_TW + 1;                         // windows evaluated
 template <typename T>
@@ -1029,27 +1029,9 @@ __global__ __launch_bounds__(256) void add_pos_kernel(float* __restrict__ x, con
     }
 }
 
-// fixed-channel forms (round 6): can the launch's grid stride (blocks x 256) be a multiple of `kq` channel groups?  May lower
-// `blocks` to make it so.  DPFT_BN_FIXC=0: off (A/B switch).
-static inline bool fixc_grid(int kq, int64_t items, int& blocks) {
-    static const int fixc = getenv("DPFT_BN_FIXC") ? atoi(getenv("DPFT_BN_FIXC")) : 2;
-    if (fixc <= 0 || items < 4096 || items >= (1ll << 30) || kq <= 0) return false;
-    if ((256 % kq) == 0) return true;
-    if ((kq % 256) != 0) return false;
-    const int f = kq / 256;
-    if (blocks < f) return false;
-    blocks -= blocks % f;
-    return true;
-}
-
 // which kernel form the dispatch below took at the last BatchNorm-family launch (dpft_bn_last_form): written where the launch is
 // made, never derived from the shape afterwards
 static int g_bn_last_form = DPFT_BN_FORM_NONE;
-
-static inline int ew_blocks(int64_t work_items) {
-    static const int per_cu = getenv("DPFT_EW_BLOCKS_PER_CU") ? atoi(getenv("DPFT_EW_BLOCKS_PER_CU")) : 8;      // tuning aid
-    return (int)std::max<int64_t>(1, std::min<int64_t>((work_items + 255) / 256, (int64_t)kNumCU * per_cu));
-}
 
 }  // namespace dpft
 
@@ -1067,10 +1049,8 @@ extern "C" int dpft_bn_finalize_f32(const float* stats, int32_t tiles, int32_t t
                                     const float* gamma, const float* beta, float eps, float momentum,
                                     float* running_mean, float* running_var, float* bnp,
                                     dpft_stream_t stream) {
-    {
-        static const char* skip = getenv("DPFT_SKIP");      // timing experiment (wrong results): the family's cost on the critical path
-        if (skip && (!strcmp(skip, "bnfinalize") || (strstr(skip, "bnfinK1024") && K >= 1024))) return DPFT_OK;
-    }
+    if (const char* skip = bn_tuning().skip)
+        if (!strcmp(skip, "bnfinalize") || (strstr(skip, "bnfinK1024") && K >= 1024)) return DPFT_OK;
     DPFT_REQUIRE(stats && gamma && beta && bnp, "bn_finalize: null tensor");
     DPFT_REQUIRE(tiles == cdiv(M, tile_rows), "bn_finalize: tiles (%d) != ceil(M/tile_rows)", tiles);
     DPFT_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "bn_finalize: running stats must come in pairs");
@@ -1102,52 +1082,35 @@ int dpft::bn_eval_params_batch(const BnEvalBatch& batch, dpft_stream_t stream) {
 
 int dpft::bn_act_any(const float* y, const float* bnp, const float* res, const float* res_bnp, int32_t relu, float* out,
                      float* out32, int64_t M, int32_t K, bool act16, dpft_stream_t stream, unsigned char* mask8) {
-    {
-        static const char* skip = getenv("DPFT_SKIP");
-        if (skip && strstr(skip, "bnact")) return DPFT_OK;
-    }
+    if (bn_skip("bnact")) return DPFT_OK;
     DPFT_REQUIRE(y && bnp && out && M > 0 && K > 0 && K % 4 == 0, "bn_act: bad arguments (K=%d)", K);
     DPFT_REQUIRE(res || !res_bnp, "bn_act: res_bnp without res");
     const int64_t n4 = M * K / 4;
-    static const bool wide16 = getenv("DPFT_BN_WIDE16") == nullptr || atoi(getenv("DPFT_BN_WIDE16")) != 0;      // A/B switch
-    if (act16 && wide16 && K % 8 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)res & 15) == 0 &&
-        ((uintptr_t)mask8 & 1) == 0)
-    {
-        int blocks = ew_blocks(n4 / 2);
-        const bool fx = fixc_grid(K / 8, n4 / 2, blocks);
-        g_bn_last_form = fx ? DPFT_BN_FORM_WIDE16_FIXC : DPFT_BN_FORM_WIDE16;
-        if (fx)
-            hipLaunchKernelGGL(bn_act16_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, y, bnp, res, res_bnp, relu, out,
-                               out32, n4 / 2, K / 8, mask8);
+    const bool aligned16 = (((uintptr_t)y | (uintptr_t)out | (uintptr_t)res) & 15) == 0 && ((uintptr_t)mask8 & 1) == 0;
+    const dpft_bn_plan plan = plan_bn_act(M, K, act16, out32 != nullptr, aligned16, bn_tuning());
+    g_bn_last_form = plan.form;
+    const dim3 grid((unsigned)plan.grid_x);
+    hipStream_t st = (hipStream_t)stream;
+    switch (plan.form) {
+    case DPFT_BN_FORM_WIDE16_FIXC:
+        hipLaunchKernelGGL(bn_act16_kernel<true>, grid, dim3(256), 0, st, y, bnp, res, res_bnp, relu, out, out32, n4 / 2, K / 8, mask8);
+        break;
+    case DPFT_BN_FORM_WIDE16:
+        hipLaunchKernelGGL(bn_act16_kernel<false>, grid, dim3(256), 0, st, y, bnp, res, res_bnp, relu, out, out32, n4 / 2, K / 8, mask8);
+        break;
+    case DPFT_BN_FORM_FIXC2:
+        hipLaunchKernelGGL((bn_act_fixc_kernel<2, false>), grid, dim3(256), 0, st, y, bnp, res, res_bnp, relu, out, n4, K / 4, mask8,
+                           BnSumsRef{}, BnSumsRef{});
+        break;
+    case DPFT_BN_FORM_FIXC1:
+        hipLaunchKernelGGL((bn_act_fixc_kernel<1, false>), grid, dim3(256), 0, st, y, bnp, res, res_bnp, relu, out, n4, K / 4, mask8,
+                           BnSumsRef{}, BnSumsRef{});
+        break;
+    default:
+        if (act16)
+            hipLaunchKernelGGL(bn_act_kernel<__bf16>, grid, dim3(256), 0, st, y, bnp, res, res_bnp, relu, out, out32, n4, K / 4, mask8);
         else
-            hipLaunchKernelGGL(bn_act16_kernel<false>, dim3(ew_blocks(n4 / 2)), dim3(256), 0, (hipStream_t)stream, y, bnp, res, res_bnp, relu, out,
-                               out32, n4 / 2, K / 8, mask8);
-    }
-    else if (act16) {
-        g_bn_last_form = DPFT_BN_FORM_GENERIC;
-        hipLaunchKernelGGL(bn_act_kernel<__bf16>, dim3(ew_blocks(n4)), dim3(256), 0, (hipStream_t)stream, y, bnp, res,
-                           res_bnp, relu, out, out32, n4, K / 4, mask8);
-    } else {
-        static const int fixc = getenv("DPFT_BN_FIXC") ? atoi(getenv("DPFT_BN_FIXC")) : 2;      // see bn_bwd_apply_zeroing
-        const int K4 = K / 4;
-        static const int fat = getenv("DPFT_BN_FAT") ? atoi(getenv("DPFT_BN_FAT")) : 1;      // two quads per thread and trip (as bn_bwd_apply)
-        int blocks = ew_blocks(fat && fixc >= 2 ? (n4 + 1) / 2 : n4);
-        bool ok = fixc > 0 && !out32 && n4 >= 4096 && n4 < (1ll << 30);
-        if (ok && (256 % K4) != 0) {
-            const int f = K4 / 256;
-            ok = (K4 % 256) == 0 && blocks >= f;
-            if (ok) blocks -= blocks % f;
-        }
-        g_bn_last_form = !ok ? DPFT_BN_FORM_GENERIC : fixc >= 2 ? DPFT_BN_FORM_FIXC2 : DPFT_BN_FORM_FIXC1;
-        if (ok && fixc >= 2)
-            hipLaunchKernelGGL((bn_act_fixc_kernel<2, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, y, bnp, res, res_bnp, relu, out, n4,
-                               K4, mask8, BnSumsRef{}, BnSumsRef{});
-        else if (ok)
-            hipLaunchKernelGGL((bn_act_fixc_kernel<1, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, y, bnp, res, res_bnp, relu, out, n4,
-                               K4, mask8, BnSumsRef{}, BnSumsRef{});
-        else
-            hipLaunchKernelGGL(bn_act_kernel<float>, dim3(ew_blocks(n4)), dim3(256), 0, (hipStream_t)stream, y, bnp, res,
-                               res_bnp, relu, out, out32, n4, K / 4, mask8);
+            hipLaunchKernelGGL(bn_act_kernel<float>, grid, dim3(256), 0, st, y, bnp, res, res_bnp, relu, out, out32, n4, K / 4, mask8);
     }
     return check_launch("bn_act");
 }
@@ -1157,29 +1120,13 @@ int dpft::bn_act_sums(const float* y, const float* bnp, const BnSumsRef& ys, con
     DPFT_REQUIRE(y && out && used && M > 0 && K > 0 && K % 4 == 0 && (bnp || ys.sums), "bn_act (column sums): bad arguments (K=%d)", K);
     DPFT_REQUIRE(res || !(res_bnp || rs.sums), "bn_act (column sums): a residual BatchNorm without a residual");
     *used = false;
-    {
-        static const char* skip = getenv("DPFT_SKIP");
-        if (skip && strstr(skip, "bnact")) { *used = true; return DPFT_OK; }
-    }
-    static const int fixc = getenv("DPFT_BN_FIXC") ? atoi(getenv("DPFT_BN_FIXC")) : 2;
-    static const int fat = getenv("DPFT_BN_FAT") ? atoi(getenv("DPFT_BN_FAT")) : 1;
-    const int64_t n4 = M * K / 4;
-    const int K4 = K / 4;
-    int blocks = ew_blocks(fat && fixc >= 2 ? (n4 + 1) / 2 : n4);
-    bool ok = fixc > 0 && n4 >= 4096 && n4 < (1ll << 30);
-    if (ok && (256 % K4) != 0) {
-        const int f = K4 / 256;
-        ok = (K4 % 256) == 0 && blocks >= f;
-        if (ok) blocks -= blocks % f;
-    }
-    g_bn_last_form = ok ? DPFT_BN_FORM_SUMS_TAKEN : DPFT_BN_FORM_SUMS_DECLINED;
-    if (!ok) return DPFT_OK;      // (the generic kernel reads BN blocks only: the caller finalizes first)
-    if (fixc >= 2)
-        hipLaunchKernelGGL((bn_act_fixc_kernel<2, true>), dim3(blocks), dim3(256), K4 < 256 ? (size_t)24 * K : 0, (hipStream_t)stream, y, bnp, res,
-                           res_bnp, relu, out, n4, K4, mask8, ys, rs);
-    else
-        hipLaunchKernelGGL((bn_act_fixc_kernel<1, true>), dim3(blocks), dim3(256), K4 < 256 ? (size_t)24 * K : 0, (hipStream_t)stream, y, bnp, res,
-                           res_bnp, relu, out, n4, K4, mask8, ys, rs);
+    if (bn_skip("bnact")) { *used = true; return DPFT_OK; }
+    const dpft_bn_plan plan = plan_bn_act_sums(M, K, bn_tuning());
+    g_bn_last_form = plan.form;
+    if (plan.form == DPFT_BN_FORM_SUMS_DECLINED) return DPFT_OK;      // (the generic kernel reads BN blocks only: the caller finalizes first)
+    auto kernel = plan.per_thread == 2 ? bn_act_fixc_kernel<2, true> : bn_act_fixc_kernel<1, true>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)plan.grid_x), dim3(256), (size_t)plan.lds_bytes, (hipStream_t)stream, y, bnp, res, res_bnp,
+                       relu, out, M * K / 4, K / 4, mask8, ys, rs);
     *used = true;
     return check_launch("bn_act (column sums)");
 }
@@ -1264,29 +1211,20 @@ extern "C" int dpft_bn_relu_maxpool_f32(const float* y, const float* bnp, float*
 int dpft::bn_relu_maxpool_bwd_any(const float* y, const float* bnp, const float* dout, float* dact, int32_t B, int32_t H,
                                   int32_t W, int32_t K, int32_t PH, int32_t PW, bool dout16, dpft_stream_t stream) {
     DPFT_REQUIRE(y && bnp && dout && dact && K % 4 == 0, "bn_relu_maxpool_bwd: bad arguments");
-    const int64_t total = (int64_t)B * H * W * (K / 4);
-    static const bool tiled = getenv("DPFT_POOL_BWD_TILED") == nullptr || atoi(getenv("DPFT_POOL_BWD_TILED")) != 0;      // A/B switch
     const int K4 = K / 4;
-    if (tiled && K4 % PB_CQ == 0 && PH == (H - 1) / 2 + 1 && PW == (W - 1) / 2 + 1) {      // 3 x 3 / stride 2 / pad 1 geometry
+    const dpft_bn_plan plan = plan_bn_pool_bwd(B, H, W, K, PH, PW, bn_tuning());
+    DPFT_REQUIRE(plan.grid_x < (1ll << 31), "bn_relu_maxpool_bwd: too many tiles");      // (the gather form's grid is capped)
+    g_bn_last_form = plan.form;
+    const dim3 grid((unsigned)plan.grid_x);
+    hipStream_t st = (hipStream_t)stream;
+    if (plan.form == DPFT_BN_FORM_POOL_TILED) {      // 3 x 3 / stride 2 / pad 1 geometry
         const int tiles_h = cdiv(H, 2 * PB_TH), tiles_w = cdiv(W, 2 * PB_TW);
-        const int64_t nb = (int64_t)B * (K4 / PB_CQ) * tiles_h * tiles_w;
-        DPFT_REQUIRE(nb < (1ll << 31), "bn_relu_maxpool_bwd: too many tiles");
-        g_bn_last_form = DPFT_BN_FORM_POOL_TILED;
-        if (dout16)
-            hipLaunchKernelGGL(bn_relu_maxpool_bwd_tiled_kernel<__bf16>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, y, bnp,
-                               dout, dact, B, H, W, K4, PH, PW, tiles_w, tiles_h);
-        else
-            hipLaunchKernelGGL(bn_relu_maxpool_bwd_tiled_kernel<float>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, y, bnp,
-                               dout, dact, B, H, W, K4, PH, PW, tiles_w, tiles_h);
+        auto kernel = dout16 ? bn_relu_maxpool_bwd_tiled_kernel<__bf16> : bn_relu_maxpool_bwd_tiled_kernel<float>;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, y, bnp, dout, dact, B, H, W, K4, PH, PW, tiles_w, tiles_h);
         return check_launch("bn_relu_maxpool_bwd (tiled)");
     }
-    g_bn_last_form = DPFT_BN_FORM_GENERIC;
-    if (dout16)
-        hipLaunchKernelGGL(bn_relu_maxpool_bwd_kernel<__bf16>, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, y,
-                           bnp, dout, dact, B, H, W, K / 4, PH, PW);
-    else
-        hipLaunchKernelGGL(bn_relu_maxpool_bwd_kernel<float>, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, y,
-                           bnp, dout, dact, B, H, W, K / 4, PH, PW);
+    auto kernel = dout16 ? bn_relu_maxpool_bwd_kernel<__bf16> : bn_relu_maxpool_bwd_kernel<float>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, y, bnp, dout, dact, B, H, W, K4, PH, PW);
     return check_launch("bn_relu_maxpool_bwd");
 }
 
@@ -1309,24 +1247,11 @@ int dpft::bn_bwd_reduce_prezeroed(const float* y, const float* dout, const float
                                   const float* bnp, float* sums, int64_t M, int32_t K, bool act16, dpft_stream_t stream,
                                   const unsigned char* mask8) {
     DPFT_REQUIRE(y && dout && bnp && sums && M > 0 && K > 0 && K % 4 == 0, "bn_bwd_reduce: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    const int K4 = K / 4;
-    // Tuned on MI355X (tools/bn_bench.py): 128 B wide channel slabs (8 float4) => 32 row groups per block and only
-    // 64 accumulators per block; at most 64 blocks per slab keeps the fp32 atomics on one accumulator <= 64-deep
-    // (the first version -- every block covering all K channels, 512 blocks -- spent most of its time in atomics).
-    const int slab = std::min(K4, 8);
-    const int slabs = cdiv(K4, slab);
-    const int groups = 256 / slab;
-    const int want_blocks = std::min(64, std::max(1, (kNumCU * 4) / slabs));
-    int64_t rows_per_block = std::max<int64_t>((int64_t)groups * 4, (M + want_blocks - 1) / want_blocks);
-    dim3 grid(cdiv(M, rows_per_block), slabs);
-    g_bn_last_form = DPFT_BN_FORM_GENERIC;
-    if (act16)
-        hipLaunchKernelGGL(bn_bwd_reduce_kernel<__bf16>, grid, dim3(256), 0, st, y, dout, out, mask_bnp, bnp, sums, M, K,
-                           (int)rows_per_block, slab, mask8);
-    else
-        hipLaunchKernelGGL(bn_bwd_reduce_kernel<float>, grid, dim3(256), 0, st, y, dout, out, mask_bnp, bnp, sums, M, K,
-                           (int)rows_per_block, slab, mask8);
+    const dpft_bn_plan plan = plan_bn_reduce(M, K, act16);
+    g_bn_last_form = plan.form;
+    auto kernel = act16 ? bn_bwd_reduce_kernel<__bf16> : bn_bwd_reduce_kernel<float>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)plan.grid_x, plan.slabs), dim3(256), 0, (hipStream_t)stream, y, dout, out, mask_bnp, bnp, sums,
+                       M, K, (int)plan.rows_per_block, plan.slab, mask8);
     return check_launch("bn_bwd_reduce");
 }
 
@@ -1343,61 +1268,27 @@ int dpft::bn_bwd_apply_zeroing(const float* y, const float* dout, const float* o
                                dpft_stream_t stream, const unsigned char* mask8, bool frozen) {
     DPFT_REQUIRE(y && dout && bnp && gamma && sums && dy && M > 0 && K % 4 == 0, "bn_bwd_apply: bad arguments");
     const int64_t n4 = M * K / 4;
-    {      // timing experiment (wrong gradients): what the pass costs on the step's critical path = the step time without it
-        static const bool skip = getenv("DPFT_BN_SKIP_APPLY") != nullptr && atoi(getenv("DPFT_BN_SKIP_APPLY")) != 0;
-        if (skip) return DPFT_OK;
-    }
+    if (bn_tuning().skip_apply) return DPFT_OK;
     // frozen (running-statistics) BatchNorm: mean and variance do not depend on the batch, so dy = gamma invstd d -- the
     // batch form with its two mean terms weighted by 1/M = 0; dgamma = sum d xhat and dbeta = sum d are the same sums
     const float invM = frozen ? 0.f : 1.0f / (float)M;
-    static const bool wide16 = getenv("DPFT_BN_WIDE16") == nullptr || atoi(getenv("DPFT_BN_WIDE16")) != 0;      // A/B switch
-    if (act16 && wide16 && K % 8 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)dout & 15) == 0 && ((uintptr_t)dy & 15) == 0 &&
-        ((uintptr_t)out & 15) == 0 && ((uintptr_t)mask8 & 1) == 0)
-    {
-        int blocks = ew_blocks(n4 / 2);
-        const bool fx = fixc_grid(K / 8, n4 / 2, blocks);
-        g_bn_last_form = fx ? DPFT_BN_FORM_WIDE16_FIXC : DPFT_BN_FORM_WIDE16;
-        if (fx)
-            hipLaunchKernelGGL(bn_bwd_apply16_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, y, dout, out, mask_bnp, bnp,
-                               gamma, sums, dy, dgamma, dbeta, n4 / 2, K, invM, zero_buf, (int)zero_n, mask8);
-        else
-            hipLaunchKernelGGL(bn_bwd_apply16_kernel<false>, dim3(ew_blocks(n4 / 2)), dim3(256), 0, (hipStream_t)stream, y, dout, out, mask_bnp, bnp,
-                               gamma, sums, dy, dgamma, dbeta, n4 / 2, K, invM, zero_buf, (int)zero_n, mask8);
+    const bool aligned16 = (((uintptr_t)y | (uintptr_t)dout | (uintptr_t)dy | (uintptr_t)out) & 15) == 0 && ((uintptr_t)mask8 & 1) == 0;
+    const dpft_bn_plan plan = plan_bn_apply(M, K, act16, aligned16, bn_tuning());
+    g_bn_last_form = plan.form;
+    // the fixed-channel kernel reads mask_bnp only where neither mask8 nor out is given: the general form only for a mask from ANOTHER block
+    const bool same = mask_bnp == bnp || !mask_bnp || mask8 || out;
+    auto kernel = bn_bwd_apply_kernel<float>;
+    int64_t n = n4;      // quads, or octets for the 16-byte forms
+    switch (plan.form) {
+    case DPFT_BN_FORM_WIDE16_FIXC: kernel = bn_bwd_apply16_kernel<true>; n = n4 / 2; break;
+    case DPFT_BN_FORM_WIDE16: kernel = bn_bwd_apply16_kernel<false>; n = n4 / 2; break;
+    case DPFT_BN_FORM_FIXC3: kernel = same ? bn_bwd_apply_fixc_kernel<3, true> : bn_bwd_apply_fixc_kernel<3, false>; break;
+    case DPFT_BN_FORM_FIXC2: kernel = same ? bn_bwd_apply_fixc_kernel<2, true> : bn_bwd_apply_fixc_kernel<2, false>; break;
+    case DPFT_BN_FORM_FIXC1: kernel = same ? bn_bwd_apply_fixc_kernel<1, true> : bn_bwd_apply_fixc_kernel<1, false>; break;
+    default: if (act16) kernel = bn_bwd_apply_kernel<__bf16>;
     }
-    else if (act16) {
-        g_bn_last_form = DPFT_BN_FORM_GENERIC;
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<__bf16>, dim3(ew_blocks(n4)), dim3(256), 0, (hipStream_t)stream, y, dout, out,
-                           mask_bnp, bnp, gamma, sums, dy, dgamma, dbeta, n4, K, invM, zero_buf, (int)zero_n, mask8);
-    } else {
-        // fixed-channel form (see bn_bwd_apply_fixc_kernel): the grid stride must be a multiple of K / 4.  DPFT_BN_FIXC=0: off; =U: quads in flight
-        static const int fixc = getenv("DPFT_BN_FIXC") ? atoi(getenv("DPFT_BN_FIXC")) : 2;
-        const int K4 = K / 4;
-        // U quads per thread and trip: a grid of n4 / (256 U) workgroups (inside the step a CU that also holds a split weight-gradient
-        // workgroup has room for ONE wave of this kernel per SIMD: the pass runs as rounds of 256 workgroups, so fewer, fatter ones)
-        static const int fat = getenv("DPFT_BN_FAT") ? atoi(getenv("DPFT_BN_FAT")) : 1;      // A/B switch
-        int blocks = ew_blocks(fat && fixc >= 2 ? (n4 + 1) / 2 : n4);
-        bool ok = fixc > 0 && n4 >= 4096 && n4 < (1ll << 30);
-        if (ok && (256 % K4) != 0) {      // K4 = 512 ...: the block count itself must carry the remaining factor
-            const int f = K4 / 256;
-            ok = (K4 % 256) == 0 && blocks >= f;
-            if (ok) blocks -= blocks % f;
-        }
-        g_bn_last_form = !ok ? DPFT_BN_FORM_GENERIC : fixc >= 3 ? DPFT_BN_FORM_FIXC3 : fixc == 2 ? DPFT_BN_FORM_FIXC2 : DPFT_BN_FORM_FIXC1;
-        // the kernel reads mask_bnp only where neither mask8 nor out is given: the general form only for a mask from ANOTHER block
-        const bool same = mask_bnp == bnp || !mask_bnp || mask8 || out;
-        auto launch = [&](auto u) {
-            constexpr int U = decltype(u)::value;
-            auto kernel = same ? bn_bwd_apply_fixc_kernel<U, true> : bn_bwd_apply_fixc_kernel<U, false>;
-            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, y, dout, out, mask_bnp, bnp, gamma, sums, dy,
-                               dgamma, dbeta, n4, K, invM, zero_buf, (int)zero_n, mask8);
-        };
-        if (ok && fixc >= 3) launch(std::integral_constant<int, 3>{});
-        else if (ok && fixc == 2) launch(std::integral_constant<int, 2>{});
-        else if (ok) launch(std::integral_constant<int, 1>{});
-        else
-            hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3(ew_blocks(n4)), dim3(256), 0, (hipStream_t)stream, y, dout, out,
-                               mask_bnp, bnp, gamma, sums, dy, dgamma, dbeta, n4, K, invM, zero_buf, (int)zero_n, mask8);
-    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)plan.grid_x), dim3(256), 0, (hipStream_t)stream, y, dout, out, mask_bnp, bnp, gamma, sums, dy,
+                       dgamma, dbeta, n, K, invM, zero_buf, (int)zero_n, mask8);
     return check_launch("bn_bwd_apply");
 }
 
@@ -1512,6 +1403,30 @@ extern "C" int dpft_cvt_f32_bf16(const float* src, void* dst, int64_t n, dpft_st
 extern "C" int dpft_bn_last_form(int32_t* form) {
     DPFT_REQUIRE(form, "bn_last_form: form is null");
     *form = g_bn_last_form;
+    return DPFT_OK;
+}
+
+extern "C" int dpft_bn_plan_query(int32_t pass, int64_t M, int32_t K, int32_t H, int32_t W, int32_t storage, int32_t flags,
+                                  const dpft_bn_switches* switches, dpft_bn_plan* plan) {
+    DPFT_REQUIRE(plan, "bn_plan_query: plan is null");
+    DPFT_BN_STORAGE("bn_plan_query", storage);
+    DPFT_REQUIRE(M > 0 && K > 0 && K % 4 == 0 && M < (1ll << 40) / K, "bn_plan_query: bad shape (M=%lld, K=%d)", (long long)M, K);
+    const BnTuning t = bn_tuning_with(switches);
+    const bool act16 = storage != 0, aligned16 = (flags & DPFT_BN_PLAN_ALIGNED16) != 0;
+    switch (pass) {
+    case DPFT_BN_PASS_ACT: *plan = plan_bn_act(M, K, act16, (flags & DPFT_BN_PLAN_OUT32) != 0, aligned16, t); break;
+    case DPFT_BN_PASS_ACT_SUMS:
+        DPFT_REQUIRE(!act16, "bn_plan_query: the column-sums pass is fp32 only");
+        *plan = plan_bn_act_sums(M, K, t);
+        break;
+    case DPFT_BN_PASS_REDUCE: *plan = plan_bn_reduce(M, K, act16); break;
+    case DPFT_BN_PASS_APPLY: *plan = plan_bn_apply(M, K, act16, aligned16, t); break;
+    case DPFT_BN_PASS_POOL_BWD:
+        DPFT_REQUIRE(H > 0 && W > 0 && M < (1ll << 31), "bn_plan_query: bad pool shape (B=%lld, H=%d, W=%d)", (long long)M, H, W);
+        *plan = plan_bn_pool_bwd((int)M, H, W, K, (H - 1) / 2 + 1, (W - 1) / 2 + 1, t);
+        break;
+    default: DPFT_REQUIRE(false, "bn_plan_query: unknown pass %d", pass);
+    }
     return DPFT_OK;
 }
 

@@ -59,7 +59,7 @@ struct ConvTuning {
     int ksplit = env("DPFT_KSPLIT", -1);                 // tuning aid: 0 / 1 force the 512-thread K-split form of igemm_vec off / on
     bool wgrad16_tiled = env("DPFT_WGRAD16_TILED", 1) != 0;      // A/B switch: LDS-tiled conv16 weight gradient
     bool wgrad_stem = env("DPFT_WGRAD_STEM", 1) != 0;    // A/B switch: LDS-tiled stem weight gradient
-    const char* skip = getenv("DPFT_SKIP");              // timing experiments: families whose launches are skipped (see skip_family)
+    const char* skip = skip_families();                  // timing experiments: families whose launches are skipped (see skip_family)
     bool thin_fwd = env("DPFT_THIN_FWD", 1) != 0;        // A/B switch: streaming 1x1 -> 16 forward
     bool bnact_fixup = env("DPFT_BNACT_FIXUP", 1) != 0;  // A/B switch: inference epilogue in the fix-up of every split vector launch
     int epf = env("DPFT_EPF", 7);                        // epilogue-operand prefetch, bits: 1 residual data gradient, 2 data gradient with a BatchNorm reduction, 4 inference residual; 0: plain epilogues (A/B switch)

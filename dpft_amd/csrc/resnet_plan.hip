@@ -341,19 +341,27 @@ static bool bn_sums_on(const ResnetPlan* p) {
 static BnSumsRef bn_sums_ref(const ResnetPlan* p, const Tables& T, float* A, int bn, int K, int64_t M) {
     return BnSumsRef{(const unsigned long long*)(A + p->o_bnacc + p->bnacc[bn]), T.gamma(bn), T.beta(bn), 1.0 / (double)M, p->desc.eps, K};
 }
-// the BN blocks + running statistics of the pending layers [from, end of the list) -- BnSumsBatch::MAX per launch
-static int bn_finalize_pending(ResnetPlan* p, const Tables& T, float* A, size_t from, dpft_stream_t st) {
+static BnSumsBatch bn_sums_batch(const ResnetPlan* p) {
     BnSumsBatch batch;
     memset(&batch, 0, sizeof(batch));
     batch.eps = p->desc.eps; batch.momentum = p->desc.momentum;
+    return batch;
+}
+// appends the pending layer `e` to the batch and takes it off the pending set
+static void bn_sums_batch_add(BnSumsBatch& batch, ResnetPlan* p, const Tables& T, float* A, const ResnetPlan::PendingBn& e) {
+    const int j = batch.n++;
+    batch.sums[j] = (const unsigned long long*)(A + p->o_bnacc + p->bnacc[e.bn]);
+    batch.gamma[j] = T.gamma(e.bn); batch.beta[j] = T.beta(e.bn); batch.rm[j] = T.rm(e.bn); batch.rv[j] = T.rv(e.bn);
+    batch.out[j] = A + e.bnp; batch.invn[j] = 1.0 / (double)e.M; batch.M[j] = e.M; batch.K[j] = e.K;
+    p->bn_pending[e.bn] = 0;
+}
+// the BN blocks + running statistics of the pending layers [from, end of the list) -- BnSumsBatch::MAX per launch
+static int bn_finalize_pending(ResnetPlan* p, const Tables& T, float* A, size_t from, dpft_stream_t st) {
+    BnSumsBatch batch = bn_sums_batch(p);
     for (size_t i = from; i < p->pend_list.size(); ++i) {
         const ResnetPlan::PendingBn& e = p->pend_list[i];
         if (!p->bn_pending[e.bn]) continue;      // (finalized on its own already: a consumer without the sums form)
-        const int j = batch.n++;
-        batch.sums[j] = (const unsigned long long*)(A + p->o_bnacc + p->bnacc[e.bn]);
-        batch.gamma[j] = T.gamma(e.bn); batch.beta[j] = T.beta(e.bn); batch.rm[j] = T.rm(e.bn); batch.rv[j] = T.rv(e.bn);
-        batch.out[j] = A + e.bnp; batch.invn[j] = 1.0 / (double)e.M; batch.M[j] = e.M; batch.K[j] = e.K;
-        p->bn_pending[e.bn] = 0;
+        bn_sums_batch_add(batch, p, T, A, e);
         if (batch.n == BnSumsBatch::MAX) {
             RC(bn_finalize_sums_batch(batch, st));
             batch.n = 0;
@@ -365,14 +373,8 @@ static int bn_finalize_pending(ResnetPlan* p, const Tables& T, float* A, size_t 
 static int bn_finalize_one(ResnetPlan* p, const Tables& T, float* A, int bn, dpft_stream_t st) {
     for (size_t i = 0; i < p->pend_list.size(); ++i)
         if (p->pend_list[i].bn == bn) {
-            BnSumsBatch batch;
-            memset(&batch, 0, sizeof(batch));
-            const ResnetPlan::PendingBn& e = p->pend_list[i];
-            batch.eps = p->desc.eps; batch.momentum = p->desc.momentum; batch.n = 1;
-            batch.sums[0] = (const unsigned long long*)(A + p->o_bnacc + p->bnacc[bn]);
-            batch.gamma[0] = T.gamma(bn); batch.beta[0] = T.beta(bn); batch.rm[0] = T.rm(bn); batch.rv[0] = T.rv(bn);
-            batch.out[0] = A + e.bnp; batch.invn[0] = 1.0 / (double)e.M; batch.M[0] = e.M; batch.K[0] = e.K;
-            p->bn_pending[bn] = 0;
+            BnSumsBatch batch = bn_sums_batch(p);
+            bn_sums_batch_add(batch, p, T, A, p->pend_list[i]);
             return bn_finalize_sums_batch(batch, st);
         }
     set_error("resnet plan: BatchNorm %d is not pending", bn);

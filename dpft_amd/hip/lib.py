@@ -132,6 +132,18 @@ class CorruptRadar(C.Structure):
                 ("rows", (C.c_int32 * 2) * CORRUPT_MAX_BANDS), ("off", C.c_int32), ("pad", C.c_int32)]
 
 
+class BnSwitches(C.Structure):
+    """dpft_bn_switches: the five dispatch switches of the BatchNorm passes (include/dpft_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("fixc", "wide16", "fat", "pool_bwd_tiled", "ew_blocks_per_cu")]
+
+
+class BnPlan(C.Structure):
+    """dpft_bn_plan: the launch a BatchNorm pass would make (dpft_bn_plan_query)."""
+    _fields_ = [("form", C.c_int32), ("per_thread", C.c_int32), ("grid_x", C.c_int64), ("grid_y", C.c_int32),
+                ("lds_bytes", C.c_int32), ("slab", C.c_int32), ("slabs", C.c_int32), ("groups", C.c_int32),
+                ("rows_per_block", C.c_int64)]
+
+
 _P, _I, _L, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 _DESC = C.POINTER(ConvDesc)
 _PYR = C.POINTER(Pyramid)
@@ -181,6 +193,7 @@ SIGNATURES = {
     "dpft_add_inplace_any_f32": (_I, [_P, _P, _L, _I, _P]),
     "dpft_cvt_f32_bf16": (_I, [_P, _P, _L, _P]),
     "dpft_bn_last_form": (_I, [C.POINTER(_I)]),
+    "dpft_bn_plan_query": (_I, [_I, _L, _I, _I, _I, _I, _I, C.POINTER(BnSwitches), C.POINTER(BnPlan)]),
     "dpft_fpn_topdown_add_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dpft_fpn_topdown_add_bwd_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dpft_add_pos_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),

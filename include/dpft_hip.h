@@ -294,6 +294,32 @@ int dpft_cvt_f32_bf16(const float* src, void* dst, int64_t n, dpft_stream_t stre
 #define DPFT_BN_FORM_SUMS_TAKEN 8       /* dpft_bn_act_sums_f32 launched its kernel */
 #define DPFT_BN_FORM_SUMS_DECLINED 9    /* ... or left the pass to the caller */
 int dpft_bn_last_form(int32_t* form);
+/* The launch a pass would make, without making it (host only, no device needed; as dpft_conv2d_planned_family): the plan the
+ * entries above build and launch from.  `pass`: DPFT_BN_PASS_*.  M rows of K channels; the pool backward takes the batch in M
+ * and its input map in H, W (the other passes ignore H, W).  `flags`: DPFT_BN_PLAN_OUT32 an fp32 copy is asked for (act),
+ * DPFT_BN_PLAN_ALIGNED16 what the entries test on their pointers: every tensor 16-byte aligned, the mask bytes 2-byte (act,
+ * apply; bf16).  `switches`: the five dispatch switches to plan under; NULL = the process's own (its DPFT_* environment). */
+#define DPFT_BN_PASS_ACT 0
+#define DPFT_BN_PASS_ACT_SUMS 1         /* dpft_bn_act_sums_f32 (fp32 only) */
+#define DPFT_BN_PASS_REDUCE 2
+#define DPFT_BN_PASS_APPLY 3
+#define DPFT_BN_PASS_POOL_BWD 4
+#define DPFT_BN_PLAN_OUT32 1
+#define DPFT_BN_PLAN_ALIGNED16 2
+typedef struct dpft_bn_switches {       /* DPFT_BN_FIXC, DPFT_BN_WIDE16, DPFT_BN_FAT, DPFT_POOL_BWD_TILED, DPFT_EW_BLOCKS_PER_CU */
+    int32_t fixc, wide16, fat, pool_bwd_tiled, ew_blocks_per_cu;
+} dpft_bn_switches;
+typedef struct dpft_bn_plan {
+    int32_t form;                       /* DPFT_BN_FORM_* */
+    int32_t per_thread;                 /* quads (16-byte bf16 forms: octets; reduce: rows) per thread and trip */
+    int64_t grid_x;                     /* workgroups of 256 threads; 0: nothing is launched (column sums declined) */
+    int32_t grid_y;
+    int32_t lds_bytes;                  /* dynamic LDS */
+    int32_t slab, slabs, groups;        /* reduce: channel quads per slab, slabs (= grid_y), row groups per workgroup */
+    int64_t rows_per_block;             /* reduce */
+} dpft_bn_plan;
+int dpft_bn_plan_query(int32_t pass, int64_t M, int32_t K, int32_t H, int32_t W, int32_t storage, int32_t flags,
+                       const dpft_bn_switches* switches, dpft_bn_plan* plan);
 
 /* ------------------------------------------------------------------------------------------
  * Native launch plan of the ResNet body (conv1/bn1/relu/maxpool/layer1..n of torchvision's

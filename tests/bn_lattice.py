@@ -131,6 +131,11 @@ def sums_launch(M, K, sw):
     return "sums_taken" if ok else "sums_declined"
 
 
+def sums_lds_bytes(K):
+    """Dynamic LDS of a taken column-sums pass: below 256 channel quads the parameters go through a table of 6 floats a channel."""
+    return 24 * K if K // 4 < 256 else 0
+
+
 def reduce_geometry(M, K, bf16):
     K4 = K // 4
     slab = min(K4, 8)

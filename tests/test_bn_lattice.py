@@ -1,8 +1,10 @@
 """The BatchNorm pass lattice (tests/bn_lattice.py) checked without a GPU: it covers the dispatch classes it claims, its fp64
 reference equals the definition written as plain loops, its exact tier is exact in float32 for every kernel expression, the float
-tier's bound holds for a float32 replay (the new C entries' refusals: tests/test_host.py).  The GPU half is
-tests/test_gpu_bn_passes.py."""
+tier's bound holds for a float32 replay (the new C entries' refusals: tests/test_host.py), and the library's launch plans
+(dpft_bn_plan_query, host only) equal the restated dispatch under every switch set.  The GPU half is tests/test_gpu_bn_passes.py."""
 import collections
+import ctypes as C
+import os
 
 import pytest
 import torch
@@ -96,3 +98,76 @@ def test_float_tier_bound_holds_for_the_float32_replay():
             if not k.startswith("fixc-uncentred") or ":frozen" in k:
                 assert v <= (2.0 if c.name in L.SELFCHECK_FULL_BOUND_ONLY else 1.0), (c.name, k, v)      # (ratios are to c / 2)
         assert w["fixc-uncentred:r1000"] > 100 * w["fixc:r1000"], (c.name, w)
+
+
+PASS_ACT, PASS_ACT_SUMS, PASS_REDUCE, PASS_APPLY, PASS_POOL_BWD = range(5)      # DPFT_BN_PASS_*
+PLAN_OUT32, PLAN_ALIGNED16 = 1, 2                                               # DPFT_BN_PLAN_*
+
+
+def _plan(lib, pas, M, K, sw, bf16=False, flags=0, H=0, W=0):
+    from dpft_amd.hip.lib import BnPlan, BnSwitches
+    switches = BnSwitches(sw["fixc"], sw["wide16"], sw["fat"], sw["tiled"], sw["per_cu"])
+    plan = BnPlan()
+    lib.call("dpft_bn_plan_query", pas, M, K, H, W, int(bf16), flags, C.byref(switches), C.byref(plan))
+    return plan
+
+
+def test_planned_launch_is_the_restated_dispatch_under_every_switch_set():
+    """The plan every BatchNorm pass launches from (bn_plan.h, asked through dpft_bn_plan_query: nothing is launched) against the
+    restatement of tests/bn_lattice.py: form, block count (with it the trim) and quads per thread of act and apply, taken /
+    declined, grid and LDS bytes of the column-sums pass, the reduce geometry, the pool backward's form -- for every case, both
+    storage types, with and without the fp32 copy, under the default switches and each one-switch change.  Integers: all exact."""
+    from dpft_amd.hip.lib import BnPlan, lib
+    from dpft_amd.hip.ops import BN_FORMS
+    cases = L.LATTICE + list(L.SUMS_CASES)
+    hit, compared = collections.Counter(), 0
+    for sw in [L.switches()] + [L.switches(**changed) for changed in L.SWITCH_RUNS]:
+        for c in cases:
+            for kind, pas in (("act", PASS_ACT), ("apply", PASS_APPLY)):
+                for bf16 in (False, True):
+                    for out32 in (False, True):
+                        want = L.elementwise_launch(kind, c.M, c.K, bf16, sw, out32)
+                        got = _plan(lib, pas, c.M, c.K, sw, bf16, PLAN_ALIGNED16 | (PLAN_OUT32 if out32 else 0))
+                        assert (BN_FORMS[got.form], got.grid_x, got.grid_y, got.per_thread, got.lds_bytes) == \
+                               (want.form, want.blocks, 1, want.per_thread, 0), (c, kind, bf16, out32, sw)
+                        hit[(kind, want.form)] += 1
+                        compared += 1
+                # tensors off 16 bytes: bf16 storage falls back to the 8-byte kernel, whatever the switches
+                want = L.elementwise_launch(kind, c.M, c.K, True, dict(sw, wide16=0))
+                got = _plan(lib, pas, c.M, c.K, sw, True, 0)
+                assert want.form == "generic" and (BN_FORMS[got.form], got.grid_x, got.per_thread) == ("generic", want.blocks, 2), (c, kind, sw)
+            form = L.sums_launch(c.M, c.K, sw)
+            got = _plan(lib, PASS_ACT_SUMS, c.M, c.K, sw)
+            assert BN_FORMS[got.form] == form, (c, sw)
+            if form == "sums_taken":
+                assert (got.grid_x, got.per_thread, got.lds_bytes) == (L.f32_fixc(c.M, c.K, sw)[1], min(sw["fixc"], 2), L.sums_lds_bytes(c.K)), (c, sw)
+            else:
+                assert (got.grid_x, got.lds_bytes) == (0, 0), (c, sw)                     # nothing is launched
+            hit[("sums", form[5:])] += 1
+            for bf16 in (False, True):
+                g = L.reduce_geometry(c.M, c.K, bf16)
+                got = _plan(lib, PASS_REDUCE, c.M, c.K, sw, bf16)
+                assert (BN_FORMS[got.form], got.slab, got.slabs, got.groups, got.rows_per_block, got.grid_x, got.grid_y, got.per_thread) == \
+                       ("generic", g["slab"], g["slabs"], g["groups"], g["rows_per_block"], g["grid_x"], g["slabs"], g["RT"]), (c, bf16)
+        for c in L.POOL_LATTICE:
+            for bf16 in (False, True):
+                got = _plan(lib, PASS_POOL_BWD, c.B, c.K, sw, bf16, H=c.H, W=c.W)
+                assert BN_FORMS[got.form] == L.pool_bwd_form(c.H, c.W, c.K, sw), (c, sw)
+    print("element-wise comparisons: %d; per (pass, form): %s" % (compared, dict(sorted(hit.items()))))
+    assert compared == len(cases) * 8 * 8
+    want_classes = {("act", f) for f in ("fixc1", "fixc2", "generic", "wide16", "wide16_fixc")} | \
+                   {("apply", f) for f in ("fixc1", "fixc2", "fixc3", "generic", "wide16", "wide16_fixc")} | \
+                   {("sums", "taken"), ("sums", "declined")}
+    assert set(hit) == want_classes, sorted(set(hit) ^ want_classes)
+    # NULL switches: the process's own (the defaults, unless the environment of this run changes them)
+    c, plan = L.by_name("sums-k1024"), BnPlan()
+    lib.call("dpft_bn_plan_query", PASS_APPLY, c.M, c.K, 0, 0, 0, 0, None, C.byref(plan))
+    want = L.elementwise_launch("apply", c.M, c.K, False, L.switches_from_env(os.environ))
+    assert (BN_FORMS[plan.form], plan.grid_x, plan.per_thread) == (want.form, want.blocks, want.per_thread)
+    # refusals: nothing is written through a bad call
+    assert lib.dpft_bn_plan_query(PASS_ACT, 16, 64, 0, 0, 0, 0, None, None) == -1 and b"plan is null" in lib.dpft_last_error()
+    assert lib.dpft_bn_plan_query(5, 16, 64, 0, 0, 0, 0, None, C.byref(plan)) == -1 and b"unknown pass" in lib.dpft_last_error()
+    assert lib.dpft_bn_plan_query(PASS_ACT, 16, 66, 0, 0, 0, 0, None, C.byref(plan)) == -1 and b"bad shape" in lib.dpft_last_error()
+    assert lib.dpft_bn_plan_query(PASS_ACT, 16, 64, 0, 0, 2, 0, None, C.byref(plan)) == -1 and b"storage" in lib.dpft_last_error()
+    assert lib.dpft_bn_plan_query(PASS_ACT_SUMS, 16, 64, 0, 0, 1, 0, None, C.byref(plan)) == -1 and b"fp32 only" in lib.dpft_last_error()
+    assert lib.dpft_bn_plan_query(PASS_POOL_BWD, 2, 64, 0, 8, 0, 0, None, C.byref(plan)) == -1 and b"bad pool shape" in lib.dpft_last_error()
