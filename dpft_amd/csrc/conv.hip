@@ -1326,8 +1326,8 @@ static int launch_igemm(IgemmArgs& a, const IgemmPlan& p, bool pro, hipStream_t 
         if constexpr (DGRAD) launch_lds(igemm_vec_kernel<64, 64, 2, 2, true, false, false>, grid, block, (size_t)(64 + 64) * LDK * sizeof(float), st, a);
         return check_launch("conv igemm (strided dgrad, all taps)");
     case kB16w: return launch_igemm_b16w(a, p.bm, p.bn, DGRAD, st);      // conv_b16w.hip: 256-row tiles, eight waves
-    case kX3Planes: return launch_igemm_x3(a, p.bm, p.bn, DGRAD, false, st);
-    case kX3: return launch_igemm_x3(a, p.bm, p.bn, DGRAD, pro, st);
+    case kX3Planes: return launch_igemm_x3(a, p.bm, p.bn, DGRAD, false, false, st);
+    case kX3: return launch_igemm_x3(a, p.bm, p.bn, DGRAD, pro, p.row3, st);
     case kPipe16:      // everything by LDS-DMA, 2-byte elements
         PIPE(128, 64, 64, true, 1) PIPE(128, 64, 64, true, 2) PIPE(64, 64, 128, true, 2) PIPE(64, 64, 64, true, 2)
         PIPE(128, 128, 64, true, 0) PIPE(128, 64, 64, true, 0) PIPE(64, 64, 128, true, 0) PIPE(64, 64, 64, true, 0)

@@ -538,7 +538,19 @@ struct WgradArgs {
 };
 
 // conv_x3.hip: the 3 x bf16 split main loop (fp32 results from the bf16 matrix cores); `a` prepared as for igemm_pipe_kernel
-int launch_igemm_x3(IgemmArgs& a, int bm, int bn, bool dgrad, bool pro, hipStream_t st);
+int launch_igemm_x3(IgemmArgs& a, int bm, int bn, bool dgrad, bool pro, bool row3, hipStream_t st);
+// conv_x3r.hip: its row-shared form (`a` as launch_igemm_x3 has rescaled it: 32-deep K-steps)
+int launch_igemm_x3r(IgemmArgs& a, int bm, int bn, bool dgrad, bool pro, hipStream_t st);
+
+// the split kernels' conversion (conv_x3.hip, conv_x3r.hip)
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+
+// (x, y) -> packed bf16 pair (RNE), and the two values it represents
+__device__ __forceinline__ unsigned cvt_pk_bf16(float x, float y) {
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{x, y}, bf16x2_t));
+}
+
 int split_planes(const float* src, void* dst, int64_t n, hipStream_t st);
 // conv_stream.hip: 1x1 convs with 64 / 128 input channels and K % 256 == 0 on large maps (weights in LDS, rows private to a wave)
 int launch_stream1x1(const dpft_conv_desc* d, const float* x, const float* w, const float* pro_bn, float* y, float* stats,

@@ -37,7 +37,7 @@ enum { kFamF32 = 0, kFamX3 = 1, kFamBf16 = 2, kFamVector = 3 };
 // compute: 0 fp32 MFMA, 1 bf16 operands, 2 3 x bf16 split; split_on: the big multi-tap GEMMs take the split kernels (2, or 0 + split switch)
 struct PlanMode { int compute; bool split_on; };
 
-// Every DPFT_* switch of conv.hip's host code, parsed once on first use (DPFT_FORCE_TILE / DPFT_FORCE_WGRAD: live, once per plan)
+// Every DPFT_* switch of conv.hip's host code, parsed once on first use (DPFT_FORCE_TILE / DPFT_FORCE_WGRAD / DPFT_X3_ROW3: live, once per plan)
 struct ConvTuning {
     static int env(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
     static int compute_env() { const char* e = getenv("DPFT_CONV_COMPUTE"); return !e ? 0 : (!strcmp(e, "bf16") ? 1 : (!strcmp(e, "bf16x3") ? 2 : 0)); }
@@ -293,8 +293,16 @@ struct IgemmPlan {
     int epf = 0, epf_kernel = 0;         // epilogue prefetch: the mode the launch qualifies for / the mode of the kernel taken
     bool vec = false, stat_sums = false, pro_from_sums = false, bnr = false;      // vector loaders; the kernel adds its statistics to column sums / can build its prologue table from column sums / carries the BatchNorm-backward reduction
     bool stream_unfit = false;           // kFwd: a streaming-1x1 shape whose bias / prologue that kernel does not take
+    bool row3 = false;                   // kX3: the row-shared main loop (x3_row3_matches)
 };
 
+// the split GEMMs whose three taps of a filter row share one staged A tile: forward and non-strided data gradient of a 3x3 / stride 1 /
+// pad 1 conv (input and output maps coincide, a tap is a shift of the flat pixel index), K-steps that do not straddle taps
+// DPFT_X3_ROW3=0|1 (A/B switch, default 1: on; read live, once per plan, like DPFT_FORCE_TILE -- tests run both forms in one process)
+inline bool x3_row3_on() { const char* e = getenv("DPFT_X3_ROW3"); return !e || atoi(e) != 0; }
+inline bool x3_row3_matches(const dpft_conv_desc* d, int gemm_c) {
+    return x3_row3_on() && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && gemm_c % 32 == 0;
+}
 inline bool x3_tile(int bm, int bn) { return (bm == 128 && (bn == 128 || bn == 64)) || (bm == 64 && bn == 64); }
 
 inline IgemmPlan plan_igemm(const dpft_conv_desc* d, IgemmKind kind, const IgemmIn& in, const PlanMode& mode) {
@@ -396,6 +404,7 @@ inline IgemmPlan plan_igemm(const dpft_conv_desc* d, IgemmKind kind, const Igemm
     } else if ((t.x3 || (mode.compute == 2 && (tn.x3_all || force.set))) && mode.compute != 1 && !x16 && !w16 && (!pro || in.pro_relu) &&
                x3_tile(t.bm, t.bn)) {
         p.kernel = kX3; p.family = kFamX3;      // fp32 results from the bf16 matrix cores: three-term split of both operands, six MFMAs
+        p.row3 = kind != kDgradClass && x3_row3_matches(d, g.C);
     } else if (pipe) {
         p.kernel = kPipe; p.family = kFamF32;
         const bool short_k = tn.shortk > 0 && g.Ktot <= tn.shortk;

@@ -27,17 +27,11 @@
 //   * the BatchNorm block of the prologue sits in LDS behind the stages (3 x C floats), read once per step.
 // Epilogue, split-K fix-up, statistics, fused BatchNorm-backward reduction and the epilogue-operand prefetch are the shared
 // ones of conv_core.h: a launch is interchangeable with igemm_pipe_kernel's.
+// 3x3 / stride 1 / pad 1 problems take the form of this loop that stages the A tile once per filter row (conv_x3r.hip, DPFT_X3_ROW3).
 #include "conv_core.h"
 
 namespace dpft {
 
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-
-// (x, y) -> packed bf16 pair (RNE), and the two values it represents
-__device__ __forceinline__ unsigned cvt_pk_bf16(float x, float y) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{x, y}, bf16x2_t));
-}
 // 4 fp32 -> three planes of 4 bf16 (8 bytes each): 22 vector instructions
 __device__ __forceinline__ void split3(const f32x4 v, u32x2& p1, u32x2& p2, u32x2& p3) {
 #pragma unroll
@@ -1135,11 +1129,13 @@ static void launch_x3(K kernel, dim3 grid, size_t lds, hipStream_t st, const Ige
 }
 
 // `a` as launch_igemm (conv.hip) has prepared it (tile counts, splits, ksteps in 64-deep units); bm x bn in {128x128, 128x64, 64x64}
-int launch_igemm_x3(IgemmArgs& a, int bm, int bn, bool dgrad, bool pro, hipStream_t st) {
+// row3: the plan chose the row-shared form (3x3, stride 1, pad 1, fp32 operands: igemm_x3r_kernel)
+int launch_igemm_x3(IgemmArgs& a, int bm, int bn, bool dgrad, bool pro, bool row3, hipStream_t st) {
     a.ksteps = a.ksteps * 2;      // 32-deep K-steps
     a.ksteps_per_split = cdiv(a.ksteps, a.splits);
     const dim3 grid(a.mtiles * a.ntiles * a.splits);
     const bool padded = a.kh * a.kw > 1 || a.pad > 0;
+    if (row3) return launch_igemm_x3r(a, bm, bn, dgrad, pro, st);      // conv_x3r.hip
     if (a.x3 && a.w3) {      // both operands arrive as planes
         DPFT_REQUIRE(!pro, "conv x3 planes: no operand prologue (the planes hold the activation)");
         DPFT_REQUIRE((int64_t)a.B * a.H * a.W * a.C * 6 < (1ll << 31) && (int64_t)a.N * a.Ktot * 6 < (1ll << 31), "conv x3 planes: operand larger than 2 GiB");
