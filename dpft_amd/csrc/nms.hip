@@ -18,6 +18,7 @@
 // same bits.
 #include "common.h"
 #include "box_iou.h"
+#include "nms_layout.h"
 
 #include <limits.h>
 #include <math.h>
@@ -239,8 +240,6 @@ __global__ __launch_bounds__(64) void nms_scan_kernel(NmsArgs a) {
     if (lane == 0) a.counts[b] = min(kept_before, a.max_det);
 }
 
-static int64_t nms_align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
 }  // namespace dpft
 
 using namespace dpft;
@@ -251,9 +250,8 @@ extern "C" int64_t dpft_nms_scratch_bytes(int32_t B, int32_t N) {
         return -1;
     }
     if (B == 0 || N == 0) return 0;
-    const int64_t W = (N + 63) / 64;
-    // mask, then box (8 floats), label, sorted, score per query, then the candidate count per frame
-    return nms_align16((int64_t)B * W * W * 64 * 8 + (int64_t)B * N * (8 + 3) * 4 + (int64_t)B * 4);
+    // mask, then box (8 floats), label, sorted, score per query, then the candidate count per frame (nms_layout.h)
+    return nms_scratch_size(B, N);
 }
 
 extern "C" int dpft_nms_f32(const float* cls, const float* center, const float* size, const float* angle, const double* iou,
@@ -275,13 +273,8 @@ extern "C" int dpft_nms_f32(const float* cls, const float* center, const float* 
     NmsArgs a;
     memset(&a, 0, sizeof(a));
     const int W = (N + 63) / 64;
-    char* p = (char*)scratch;
-    a.mask = (unsigned long long*)p; p += (int64_t)B * W * W * 64 * 8;
-    a.box = (float*)p;               p += (int64_t)B * N * 8 * 4;
-    a.label = (int*)p;               p += (int64_t)B * N * 4;
-    a.sorted = (int*)p;              p += (int64_t)B * N * 4;
-    a.score = (float*)p;             p += (int64_t)B * N * 4;
-    a.ndet = (int*)p;
+    const NmsScratch sc = nms_scratch_layout(scratch, B, N);
+    a.mask = sc.mask; a.box = sc.box; a.label = sc.label; a.sorted = sc.sorted; a.score = sc.score; a.ndet = sc.ndet;
     a.cls = cls; a.center = center; a.size = size; a.angle = angle;
     a.status = status; a.order = order; a.counts = counts; a.cls_out = cls_out;
     a.thr = *iou; a.min_score = min_score; a.kind = kind; a.agnostic = class_agnostic != 0; a.max_det = max_det;

@@ -1,7 +1,8 @@
 """Data-parallel evaluation loop: the counterpart of ``CentralizedEvaluator`` (src/dprt/evaluation/evaluator.py:19-214) on this
 package's device-side pieces.
 
-``evaluate_one_epoch`` (evaluator.py:138-177) = eval-mode forward -> [``RotatedNMS``, only with ``evaluate.nms`` set: three
+``evaluate_one_epoch`` (evaluator.py:138-177) = eval-mode forward [with ``evaluate.tta`` set: T forwards and the fusion of tta.py, five
+launches per batch, in the place of every forward] -> [``RotatedNMS``, only with ``evaluate.nms`` set: three
 launches per batch, nms.py] -> ``Metric`` (two launches per batch) -> exporter (one
 selection launch per batch and threshold chunk) for every batch of the test split.  Under ``torch.distributed`` every rank
 takes a CONTIGUOUS block of the split (``BlockShardedSampler``: sample k keeps the file name it has in a one-process run),
@@ -61,18 +62,22 @@ class DataParallelEvaluator:
 
     def __init__(self, metric: Optional[torch.nn.Module] = None, exporter: Optional[Callable] = None,
                  device: Optional[torch.device] = None, logging: Optional[str] = None, dataset_ap=None, nms=None,
-                 robustness=None):
+                 robustness=None, tta=None):
         """``logging``: None, 'step' or 'epoch' (evaluator.py:24-28).  ``dataset_ap``: an optional
         ``dpft_amd.evaluation.dataset_ap.DatasetAP`` -- split-level AP_BEV / AP_3D accumulated beside the per-step metrics.
         ``nms``: an optional ``dpft_amd.evaluation.nms.RotatedNMS`` -- the metric, the split-level AP and the exporter then read
         ``nms.suppress(output)`` instead of the model's raw output (not in the reference: its numbers and files differ).
         ``robustness``: an optional ``dpft_amd.evaluation.robustness.RobustnessSuite`` -- after a batch's clean pass every
         condition runs one more forward on the degraded batch and feeds its own metric sums and split-level AP
-        (``{key}/cond={name}``); K conditions cost K extra forwards per batch.  The exporter sees the clean output only."""
+        (``{key}/cond={name}``); K conditions cost K extra forwards per batch.  The exporter sees the clean output only.
+        ``tta``: an optional ``dpft_amd.evaluation.tta.TestTimeAugmentation`` -- every forward of ``evaluate_one_epoch`` (the
+        conditions' included: the views are taken from the degraded batch) becomes T forwards fused into one (B, T N) output,
+        in front of ``nms`` (not in the reference either).  Inference time and complexity stay the plain model's."""
         self.eval_fn, self.export_fn, self.logging = metric, exporter, logging
         self.dataset_ap = dataset_ap
         self.nms = nms
         self.robustness = robustness
+        self.tta = tta
         self.condition_ap: Dict[str, Any] = {}
         self.device = torch.device(device) if device is not None else torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
         self.rank = dist.get_rank() if dist.is_initialized() else 0
@@ -93,11 +98,15 @@ class DataParallelEvaluator:
         if config.get("evaluate", {}).get("robustness"):          # (absent or false: nothing is imported or built)
             from dpft_amd.evaluation.robustness import RobustnessSuite
             robustness = RobustnessSuite.from_config(config)
+        tta = None
+        if config.get("evaluate", {}).get("tta"):                 # (absent or false: nothing is imported or built)
+            from dpft_amd.evaluation.tta import TestTimeAugmentation
+            tta = TestTimeAugmentation.from_config(config)
         return cls(metric=build_metric(config["evaluate"]),
                    exporter=build_exporter(config["evaluate"]["exporter"]["name"], config),
                    device=device, logging=config["train"].get("logging"),
                    dataset_ap=DatasetAP.from_config(config),      # (None unless evaluate.dataset_ap is set)
-                   nms=nms, robustness=robustness)
+                   nms=nms, robustness=robustness, tta=tta)
 
     def __call__(self, *args, **kwargs):
         return self.evaluate(*args, **kwargs)
@@ -150,7 +159,7 @@ class DataParallelEvaluator:
         for i, (data, labels) in enumerate(data_loader):
             labels = [self._dict_to(l) for l in labels]
             data = self._dict_to(data)
-            output = model(data)
+            output = model(data) if self.tta is None else self.tta(model, data)
             if self.nms is not None:                    # duplicates read as background to all three consumers below
                 output = self.nms.suppress(output)
             metrics = self.eval_fn(output, labels) if self.eval_fn is not None else {}
@@ -164,7 +173,8 @@ class DataParallelEvaluator:
             if self.export_fn is not None and root is not None:
                 self.export_fn(output, labels, shard_start + seen, root)
             for name in conditions:                     # one more forward per condition; the clean pass above is untouched
-                out_c = model(self.robustness.apply(name, data, shard_start + seen))
+                data_c = self.robustness.apply(name, data, shard_start + seen)
+                out_c = model(data_c) if self.tta is None else self.tta(model, data_c)
                 if self.nms is not None:
                     out_c = self.nms.suppress(out_c)
                 for k, v in (self.eval_fn(out_c, labels) if self.eval_fn is not None else {}).items():

@@ -132,6 +132,15 @@ class CorruptRadar(C.Structure):
                 ("rows", (C.c_int32 * 2) * CORRUPT_MAX_BANDS), ("off", C.c_int32), ("pad", C.c_int32)]
 
 
+TTA_MAX_VIEWS = 4      # DPFT_TTA_MAX_VIEWS
+
+
+class TtaViews(C.Structure):
+    """dpft_tta_views: the T views' output tensors and flip flags (include/dpft_hip.h)."""
+    _fields_ = [("cls", C.c_void_p * TTA_MAX_VIEWS), ("center", C.c_void_p * TTA_MAX_VIEWS), ("size", C.c_void_p * TTA_MAX_VIEWS),
+                ("angle", C.c_void_p * TTA_MAX_VIEWS), ("flip", C.c_int32 * TTA_MAX_VIEWS)]
+
+
 class BnSwitches(C.Structure):
     """dpft_bn_switches: the five dispatch switches of the BatchNorm passes (include/dpft_hip.h)."""
     _fields_ = [(n, C.c_int32) for n in ("fixc", "wide16", "fat", "pool_bwd_tiled", "ew_blocks_per_cu")]
@@ -265,6 +274,9 @@ SIGNATURES = {
     "dpft_dataset_ap_finalize_tp_groups_f64": (_I, [_P, _P, _P, _L, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "dpft_nms_scratch_bytes": (_L, [_I, _I]),
     "dpft_nms_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "dpft_tta_scratch_bytes": (_L, [_I, _I, _I]),
+    "dpft_tta_gather_f32": (_I, [C.POINTER(TtaViews), _I, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "dpft_tta_vote_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "dpft_radar_projection_scratch_floats": (_L, [_I, _I, _I, _I]),
     "dpft_export_select_f32": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
     "dpft_radar_projection_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),

@@ -216,6 +216,12 @@ class DataParallelTrainer:
         if config.get("evaluate", {}).get("nms"):
             from dpft_amd.evaluation.nms import RotatedNMS
             self.nms = RotatedNMS.from_config(config)
+        # optional test-time augmentation in front of it (evaluate.tta; evaluation/tta.py): T forwards per validation batch fused
+        # into one (B, T N) output; the validation loss keeps reading the raw output of view 0
+        self.tta = None
+        if config.get("evaluate", {}).get("tta"):
+            from dpft_amd.evaluation.tta import TestTimeAugmentation
+            self.tta = TestTimeAugmentation.from_config(config)
         opt = dict(train["optimizer"])
         name = opt.pop("name")
         self.world = dist.get_world_size() if dist.is_initialized() else 1
@@ -638,8 +644,12 @@ class DataParallelTrainer:
         for i, (data, labels) in enumerate(data_loader):
             labels = [self._dict_to(l) for l in labels]
             data = self._dict_to(data)
-            output = self.model(data)
+            tta = getattr(self, "tta", None) if (self.eval_fn is not None or self.dataset_ap is not None) else None
+            views = tta.forwards(self.model, data) if tta is not None else None
+            output = self.model(data) if views is None else views[0]
             loss, losses = self.loss_fn(output, labels)
+            if views is not None:
+                output = tta.fuse(views)
             if self.nms is not None and (self.eval_fn is not None or self.dataset_ap is not None):
                 output = self.nms.suppress(output)
             metrics = self.eval_fn(output, labels) if self.eval_fn is not None else {}

@@ -1176,6 +1176,44 @@ int dpft_nms_f32(const float* cls, const float* center, const float* size, const
                  int32_t kind, int32_t class_agnostic, float min_score, int32_t max_det, void* scratch,
                  int32_t* status, int32_t* order, int32_t* counts, float* cls_out, int32_t B, int32_t N, int32_t C,
                  dpft_stream_t stream);
+/* The scratch after dpft_nms_f32, a contract for dpft_tta_vote_f32 (csrc/nms_layout.h spells the offsets): with
+ * W = ceil(N / 64), in this order and unpadded, mask (B,W,W,64) uint64, then in SORTED order per sample (score desc,
+ * query asc; only the first ndet[b] entries of sample b are written) box (B,N,8) float = center, size, angle,
+ * label (B,N) int32, sorted (B,N) int32 = query index, score (B,N) float, and ndet (B) int32. */
+
+/* ------------------------------------------------------------------------------------------
+ * Test-time augmentation: the fusion of T views' outputs (optional, "evaluate.tta"; dpft_amd/evaluation/tta.py states
+ * the definition, tests/tta_ref.py restates it).  T = 2 .. DPFT_TTA_MAX_VIEWS views of N queries, view 0 the identity;
+ * M = T N <= 1024 candidates, id m = t N + n; 2 <= C <= 16.  Per batch gather, dpft_nms_f32 on the union, vote: five
+ * launches on `stream`, no read-back, no atomics -- the same input gives the same bits.
+ * dpft_tta_gather_f32: the views' tensors (B,N,C) (B,N,3) (B,N,3) (B,N,2) -> the union tensors (B,M,.); a view with
+ *   flip != 0 has the sign bit of center[1] and angle[0] flipped.  The pointers travel by value in the kernel arguments.
+ * clustering: dpft_nms_f32(union..., iou, kind, 0, min_score, INT32_MAX, scratch, status, order, counts, cls_out, B, M, C)
+ *   with scratch of dpft_tta_scratch_bytes(B, N, T) (= dpft_nms_scratch_bytes(B, M)) bytes.
+ * dpft_tta_vote_f32: reads the union, `status` and the sorted arrays of `scratch`.  A kept candidate heads a cluster, its
+ *   members are the candidates whose status names it, visited in sorted order, head first.  w_i = (double) s_i if
+ *   0 < s_i < inf else 0.  A head with n >= 2 members and sum w > 0: center and size = sum w_i x_i / sum w_i; angle =
+ *   sum' w_i u_i / sum' w_i, u_i = (sin, cos) / sqrt(sin^2 + cos^2), sum' leaving out members with u_i . u_head < 0
+ *   (sum' w = 0: the head's angle); all in fp64, sequential, rounded to fp32 once.  Otherwise the head's 8 floats.
+ *   score 0 (mean): sum s_i / max(n, T) in fp64, rounded once; 1 (max): the head's score.  A head's row of cls_out
+ *   (dpft_nms_f32's, rewritten in place) becomes zeros but [c] = the fused score; every other row of cls_out stays
+ *   dpft_nms_f32's; center_out / size_out / angle_out (B,M,.) hold the union's bits in every row that is no head.
+ *   members (B,M) int32: n in a head's row, 0 elsewhere.
+ * ---------------------------------------------------------------------------------------- */
+#define DPFT_TTA_MAX_VIEWS 4
+typedef struct dpft_tta_views {
+    const float* cls[DPFT_TTA_MAX_VIEWS];
+    const float* center[DPFT_TTA_MAX_VIEWS];
+    const float* size[DPFT_TTA_MAX_VIEWS];
+    const float* angle[DPFT_TTA_MAX_VIEWS];
+    int32_t flip[DPFT_TTA_MAX_VIEWS];
+} dpft_tta_views;
+int64_t dpft_tta_scratch_bytes(int32_t B, int32_t N, int32_t T);      /* -1 + dpft_last_error() when out of range */
+int dpft_tta_gather_f32(const dpft_tta_views* views, int32_t T, float* cls, float* center, float* size, float* angle,
+                        int32_t B, int32_t N, int32_t C, dpft_stream_t stream);
+int dpft_tta_vote_f32(const float* center, const float* size, const float* angle, const int32_t* status,
+                      const void* scratch, int32_t score, int32_t T, float* cls_out, float* center_out, float* size_out,
+                      float* angle_out, int32_t* members, int32_t B, int32_t N, int32_t C, dpft_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * K-Radar export selection: KRadarExporter._construct_objects
