@@ -25,7 +25,19 @@
 // position, zeros for every other record.  Integer sums are exact and order-free, so the finalize (one workgroup per class, or per
 // (group, class): block scan of the TP bit and of the four integers, cumulative means at the recall points) gives a group the bits
 // of an ungrouped run over its frames, and a merge of ranks cannot move a bit.
+//
+// KITTI-protocol table (optional, the *_kitti entries; the protocol and its two reductions are stated in
+// dpft_amd/evaluation/dataset_ap.py, tests/dataset_ap_kitti_ref.py holds the literal two passes).  After the walk above the wave
+// that owns a combination walks twice more: pass 1 (target-major, every target takes the first unassigned detection in score
+// order above the threshold) sets bit 8 + k of the record's fourth word, pass 2 (the detections inserted in score order into a
+// maintained target-major largest-IoU matching, a displaced detection offered on to the later targets) sets bit 16 + k when the
+// insertion adds a matched target.  Over the split's ordered records the protocol is then two prefix sums: the pass-1 bits rank
+// the TP scores the <= 41 thresholds are picked from (ap_kitti.h), the pass-2 bits up to the end of a threshold's score tie group
+// are its TP count.  The one-bit form of pass 2 holds ONLY because no detection is ever ignored (the exporter writes one
+// difficulty and no don't-care region): with KITTI's neighbouring classes or don't-care areas an unmatched detection may or may
+// not count as an FP depending on the threshold, and a per-detection bit cannot say that.
 #include "common.h"
+#include "ap_kitti.h"
 #include "box_iou.h"
 
 #include <limits.h>
@@ -149,8 +161,84 @@ __global__ __launch_bounds__(128) void ap_pair_kernel(ApArgs a) {
     a.pair[idx * 2 + 1] = d3;
 }
 
+// The two KITTI walks of combination k by one wave (the protocol: dpft_amd/evaluation/dataset_ap.py).  Every loop is bounded by M
+// or D and nothing waits on another wave; the bits go into tp[] with LDS atomics like the walk's own.
+__device__ __forceinline__ void ap_kitti_walks(const ApArgs& a, const double* pair, const unsigned long long* key,
+                                               const float* score, const unsigned char* cand, const unsigned* tcand, unsigned* tp,
+                                               int D, int M, int k, int lane) {
+    const double thr = a.thr[k];
+    const int kd = a.kind[k];
+    // ---- pass 1: targets in ascending index; each takes the first unassigned detection in (score desc, query asc) order with
+    //      IoU > thr and score >= 0 (the tool's pass-1 score threshold).  Lane holds the assigned bits of the sorted detections
+    //      lane, lane + 64, ...: D <= 1024 gives 16 bits ----
+    unsigned taken = 0;
+    for (int j = 0; j < M; ++j) {
+        if (!((tcand[j] >> k) & 1u)) continue;                          // (uniform over the wave)
+        for (int ch = 0; ch * 64 < D; ++ch) {
+            const int i = ch * 64 + lane;
+            bool ok = false;
+            if (i < D && ((cand[i] >> k) & 1) && !((taken >> ch) & 1u)) {
+                const unsigned q = (unsigned)key[i];
+                ok = score[q] >= 0.f && pair[((int64_t)q * a.Mmax + j) * 2 + kd] > thr;
+            }
+            const unsigned long long bal = __ballot(ok);
+            if (bal) {
+                if (lane == __ffsll((long long)bal) - 1) {
+                    taken |= 1u << ch;
+                    atomicOr(&tp[i], 0x100u << k);
+                }
+                break;
+            }
+        }
+    }
+    // ---- pass 2: the detections enter in score order; lane holds targets lane + 64 t with the query and the IoU of the detection
+    //      matched to each.  The entering detection goes to the lowest target (from `start`) that is above the threshold and is
+    //      free, or holds a smaller IoU, or an equal one from a higher query; a displaced detection is offered on from the next
+    //      target.  The chain ends at a free target (the entering detection gets its bit) or when nobody takes (no bit) ----
+    int mq[4] = {-1, -1, -1, -1};
+    double mv[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = 0; i < D; ++i) {
+        if (!((cand[i] >> k) & 1)) continue;                            // (uniform over the wave)
+        int xq = (int)(unsigned)key[i];
+        int start = 0;
+        for (int step = 0; step < M; ++step) {                          // (every step moves `start` up: at most M)
+            const double* row = pair + (int64_t)xq * a.Mmax * 2 + kd;
+            int bj = INT_MAX;
+            double bv = 0.0;
+#pragma unroll
+            for (int t = 3; t >= 0; --t) {                              // (descending: the lowest taking target of the lane stays)
+                const int j = lane + 64 * t;
+                if (j >= start && j < M) {
+                    const double v = row[2 * j];
+                    if (v > thr && (mq[t] < 0 || v > mv[t] || (v == mv[t] && xq < mq[t]))) { bj = j; bv = v; }
+                }
+            }
+            int lo = bj;
+            for (int o = 32; o > 0; o >>= 1) lo = min(lo, __shfl_xor(lo, o));
+            if (lo == INT_MAX) break;
+            int old = -1;
+            if (lane == (lo & 63)) {                                    // (this lane's bj is lo: the lowest of the wave is the lane's lowest)
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+                    if (t == (lo >> 6)) { old = mq[t]; mq[t] = xq; mv[t] = bv; }
+            }
+            old = __shfl(old, lo & 63);
+            if (old < 0) {
+                if (lane == 0) atomicOr(&tp[i], 0x10000u << k);
+                break;
+            }
+            xq = old;
+            start = lo + 1;
+        }
+    }
+}
+
 // `g` is a compile-time null in ap_match_kernel: the frame row below exists in the *_groups kernels only; `t` is one in the kernels
-// without true-positive errors: the matched target index and the error rows exist in the *_tp kernels only
+// without true-positive errors: the matched target index and the error rows exist in the *_tp kernels only; `kitti` is a template
+// argument, false in the four kernels without the KITTI walks: nothing of the walks is instantiated in them and `tcand`, which only
+// the `if constexpr (kitti)` parts touch, takes no LDS there (the kernels' assembly and LDS sizes were compared with the ones from
+// before the walks existed when this was written: equal); in the *_kitti kernels `t` is a runtime null
+template <bool kitti>
 __device__ __forceinline__ void ap_match_body(const ApArgs& a, const ApGroupArgs* g, const ApTpArgs* t) {
     __shared__ unsigned long long key[kApMaxN];      // (score descending, query ascending) as one ascending integer
     __shared__ float score[kApMaxN];
@@ -158,6 +246,7 @@ __device__ __forceinline__ void ap_match_body(const ApArgs& a, const ApGroupArgs
     __shared__ unsigned char label[kApMaxN];
     __shared__ unsigned char cand[kApMaxN];          // per sorted detection: bit k = some target lies above threshold k
     __shared__ unsigned char match[kApMaxN];         // per sorted detection: the target the reference combination took (t only)
+    __shared__ unsigned tcand[kApMaxM];              // per target: bit k = some detection lies above threshold k (kitti only)
     __shared__ int npos[kApMaxC];
     __shared__ int s_D, s_nan;
     __shared__ long long s_base;
@@ -204,13 +293,23 @@ __device__ __forceinline__ void ap_match_body(const ApArgs& a, const ApGroupArgs
     }
     // ---- which detections have a candidate at all (the walk below only stops at those) ----
     const double* pair = a.pair + (int64_t)b * N * a.Mmax * 2;
+    if constexpr (kitti) {
+        for (int j = tid; j < M; j += 256) tcand[j] = 0u;
+        __syncthreads();
+    }
     for (int i = tid; i < D; i += 256) {
         const double* row = pair + (int64_t)(unsigned)key[i] * a.Mmax * 2;
         unsigned bits = 0;
         for (int j = 0; j < M; ++j) {
             const double v0 = row[2 * j], v1 = row[2 * j + 1];
+            unsigned seen = 0;
+            if constexpr (kitti) { seen = bits; bits = 0; }            // (this target's bits alone, for its side of the table)
             for (int k = 0; k < a.K; ++k)
                 if ((a.kind[k] ? v1 : v0) > a.thr[k]) bits |= 1u << k;
+            if constexpr (kitti) {
+                if (bits) atomicOr(&tcand[j], bits);
+                bits |= seen;
+            }
         }
         cand[i] = (unsigned char)bits;
         tp[i] = 0u;
@@ -244,6 +343,7 @@ __device__ __forceinline__ void ap_match_body(const ApArgs& a, const ApGroupArgs
                 if (t && k == t->ref_k && lane == 0) match[i] = (unsigned char)bj;
             }
         }
+        if constexpr (kitti) ap_kitti_walks(a, pair, key, score, cand, tcand, tp, D, M, k, lane);
     }
     __syncthreads();
     // ---- append: one cursor atomic per workgroup ----
@@ -281,13 +381,22 @@ __device__ __forceinline__ void ap_match_body(const ApArgs& a, const ApGroupArgs
     }
 }
 
-__global__ __launch_bounds__(256) void ap_match_kernel(ApArgs a) { ap_match_body(a, nullptr, nullptr); }
+__global__ __launch_bounds__(256) void ap_match_kernel(ApArgs a) { ap_match_body<false>(a, nullptr, nullptr); }
 
-__global__ __launch_bounds__(256) void ap_match_groups_kernel(ApArgs a, ApGroupArgs g) { ap_match_body(a, &g, nullptr); }
+__global__ __launch_bounds__(256) void ap_match_groups_kernel(ApArgs a, ApGroupArgs g) { ap_match_body<false>(a, &g, nullptr); }
 
-__global__ __launch_bounds__(256) void ap_match_tp_kernel(ApArgs a, ApTpArgs t) { ap_match_body(a, nullptr, &t); }
+__global__ __launch_bounds__(256) void ap_match_tp_kernel(ApArgs a, ApTpArgs t) { ap_match_body<false>(a, nullptr, &t); }
 
-__global__ __launch_bounds__(256) void ap_match_groups_tp_kernel(ApArgs a, ApGroupArgs g, ApTpArgs t) { ap_match_body(a, &g, &t); }
+__global__ __launch_bounds__(256) void ap_match_groups_tp_kernel(ApArgs a, ApGroupArgs g, ApTpArgs t) { ap_match_body<false>(a, &g, &t); }
+
+// the match pass with the two KITTI walks; has_t = 0: no true-positive errors (a runtime null)
+__global__ __launch_bounds__(256) void ap_match_kitti_kernel(ApArgs a, ApTpArgs t, int has_t) {
+    ap_match_body<true>(a, nullptr, has_t ? &t : nullptr);
+}
+
+__global__ __launch_bounds__(256) void ap_match_kitti_groups_kernel(ApArgs a, ApGroupArgs g, ApTpArgs t, int has_t) {
+    ap_match_body<true>(a, &g, has_t ? &t : nullptr);
+}
 
 struct ApFinalArgs {
     const int4* rec;                       // ordered by (class, score desc, frame, query)
@@ -536,6 +645,139 @@ __global__ __launch_bounds__(256) void ap_finalize_tp_kernel(ApTpFinalArgs a) {
     }
 }
 
+struct ApKittiFinalArgs {
+    const int4* rec;                       // ordered by (class, score desc, frame, query)
+    const unsigned* rec_groups;            // (n) group mask of every record's frame, or null: every record is a member
+    const long long* class_start;          // (C + 1)
+    const unsigned long long* counters;    // ground truth per class (without groups)
+    const double* group_npos;              // (G, C-1) ground truth per group and class (with groups)
+    double *ap40, *ap11;                   // (G, C-1, K)
+    double *prec, *recall, *thresholds, *tp, *fp;      // (G, C-1, K, 41)
+    int32_t* nthr;                         // (G, C-1, K)
+    long long n;
+    int G, C, K;
+};
+
+// One workgroup per (group, class, combination) over the member records, three trips over them:
+//  A  n1 = number of pass-1 bits; thread 0 then picks the ranks of the <= 41 thresholds (ap_kitti_ranks: a function of n1 and npos);
+//  B  block prefix sum of the pass-1 bit: the record whose rank was picked gives the threshold its score;
+//  C  every member goes into the bin of the first threshold its score reaches (thresholds descend, equal ones leave the later bin
+//     empty), with its pass-2 bit beside it: integer counts.  Their running sums over the bins are A = the detections with
+//     score >= s up to the END of the threshold's tie group and TP = the pass-2 bits among them; FP = A - TP.
+// Then prec = TP / A, rec = TP / G, suffix maximum, AP (R40) and AP11, summed in ascending i by one thread.
+__global__ __launch_bounds__(256) void ap_finalize_kitti_kernel(ApKittiFinalArgs a) {
+    __shared__ int wsum[4];
+    __shared__ long long ranks[kApKittiPoints];
+    __shared__ float thr[kApKittiPoints];
+    __shared__ unsigned long long cnt_a[kApKittiPoints], cnt_tp[kApKittiPoints];
+    __shared__ int s_nt;
+    const int k = blockIdx.x % a.K, gc = blockIdx.x / a.K, c = 1 + gc % (a.C - 1), g = gc / (a.C - 1);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long s = min(max(a.class_start[c], 0ll), a.n), e = min(max(a.class_start[c + 1], s), a.n);
+    const long long np = a.rec_groups ? (long long)a.group_npos[g * (a.C - 1) + c - 1] : (long long)a.counters[kApNpos + c];
+    if (tid < kApKittiPoints) { cnt_a[tid] = 0ull; cnt_tp[tid] = 0ull; thr[tid] = 0.f; }
+    // ---- A ----
+    long long n1 = 0;
+    for (long long base = s; base < e; base += 256) {
+        const long long p = base + tid;
+        const bool mem = p < e && (!a.rec_groups || ((a.rec_groups[p] >> g) & 1u));
+        const bool bit = mem && ((a.rec[p].w >> (8 + k)) & 1);
+        const unsigned long long bal = __ballot(bit);
+        if (lane == 0) wsum[wave] = __popcll(bal);
+        __syncthreads();
+        for (int w = 0; w < 4; ++w) n1 += wsum[w];
+        __syncthreads();
+    }
+    if (tid == 0) s_nt = np > 0 ? ap_kitti_ranks(n1, np, ranks) : 0;
+    __syncthreads();
+    const int nt = s_nt;
+    // ---- B ----
+    long long carry = 0;
+    for (long long base = s; base < e && nt > 0; base += 256) {
+        const long long p = base + tid;
+        const bool mem = p < e && (!a.rec_groups || ((a.rec_groups[p] >> g) & 1u));
+        const bool bit = mem && ((a.rec[p].w >> (8 + k)) & 1);
+        const unsigned long long bal = __ballot(bit);
+        if (lane == 0) wsum[wave] = __popcll(bal);
+        __syncthreads();
+        int off = 0, tot = 0;
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) off += wsum[w];
+            tot += wsum[w];
+        }
+        if (bit) {
+            const long long rank = carry + off + __popcll(bal & ((2ull << lane) - 1ull)) - 1;      // 0-based
+            for (int t = 0; t < nt; ++t)
+                if (ranks[t] == rank) thr[t] = __int_as_float(a.rec[p].x);
+        }
+        carry += tot;
+        __syncthreads();
+    }
+    __syncthreads();
+    // ---- C ----
+    for (long long base = s; base < e && nt > 0; base += 256) {
+        const long long p = base + tid;
+        const bool mem = p < e && (!a.rec_groups || ((a.rec_groups[p] >> g) & 1u));
+        int bin = nt;
+        bool hit = false;
+        if (mem) {
+            const int4 r = a.rec[p];
+            const float sc = __int_as_float(r.x);
+            hit = (r.w >> (16 + k)) & 1;
+            for (int t = nt - 1; t >= 0; --t)
+                if (sc >= thr[t]) bin = t;                              // the first threshold the score reaches
+        }
+        const unsigned long long hits = __ballot(hit);
+        unsigned long long todo = __ballot(bin < nt);
+        while (todo) {                                                  // one LDS atomic pair per distinct bin of the wave
+            const int leader = __ffsll((long long)todo) - 1;
+            const int lb = __shfl(bin, leader);
+            const unsigned long long same = __ballot(bin == lb) & todo;
+            if (lane == leader) {
+                atomicAdd(&cnt_a[lb], (unsigned long long)__popcll(same));
+                atomicAdd(&cnt_tp[lb], (unsigned long long)__popcll(same & hits));
+            }
+            todo &= ~same;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int o = (g * (a.C - 1) + c - 1) * a.K + k;
+        double* prec = a.prec + (long long)o * kApKittiPoints;
+        double* recall = a.recall + (long long)o * kApKittiPoints;
+        double* thrs = a.thresholds + (long long)o * kApKittiPoints;
+        double* tp = a.tp + (long long)o * kApKittiPoints;
+        double* fp = a.fp + (long long)o * kApKittiPoints;
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        double env[kApKittiPoints];
+        unsigned long long A = 0, T = 0;
+        for (int t = 0; t < kApKittiPoints; ++t) {
+            if (t < nt) {
+                A += cnt_a[t];
+                T += cnt_tp[t];
+                prec[t] = (double)T / (double)A;
+                recall[t] = (double)T / (double)np;
+                thrs[t] = (double)thr[t];
+                tp[t] = (double)T;
+                fp[t] = (double)(A - T);
+            } else {
+                prec[t] = 0.0; recall[t] = 0.0; thrs[t] = nan; tp[t] = 0.0; fp[t] = 0.0;
+            }
+        }
+        double m = 0.0;
+        for (int t = kApKittiPoints - 1; t >= 0; --t) {                 // suffix maximum
+            m = fmax(m, prec[t]);
+            env[t] = m;
+        }
+        double s40 = 0.0, s11 = 0.0;
+        for (int t = 1; t <= 40; ++t) s40 += env[t];
+        for (int t = 0; t <= 40; t += 4) s11 += env[t];
+        a.ap40[o] = np > 0 ? s40 / 40.0 : nan;
+        a.ap11[o] = np > 0 ? s11 / 11.0 : nan;
+        a.nthr[o] = nt;
+    }
+}
+
 static bool ap_sizes_ok(int B, int N, int Mmax, int C) {
     return B > 0 && N > 0 && N <= kApMaxN && Mmax > 0 && Mmax <= kApMaxM && C >= 2 && C <= kApMaxC;
 }
@@ -604,7 +846,7 @@ static int ap_update(const float* cls, const float* center, const float* size, c
                      const int32_t* gt_id, const int32_t* counts, const double* iou_thrs, const int32_t* kinds, int32_t K,
                      const float* roi6, float min_score, void* scratch, void* records, int64_t capacity, int64_t reserved,
                      int64_t* counters, int32_t first_frame, int32_t B, int32_t N, int32_t Mmax, int32_t C, const ApTpArgs* t,
-                     dpft_stream_t stream) {
+                     bool kitti, dpft_stream_t stream) {
     ApArgs a;
     int rc = ap_fill_update(a, cls, center, size, angle, gt_box, gt_id, counts, iou_thrs, kinds, K, roi6, min_score, scratch, records,
                             capacity, reserved, counters, first_frame, B, N, Mmax, C);
@@ -613,7 +855,11 @@ static int ap_update(const float* cls, const float* center, const float* size, c
     hipLaunchKernelGGL(ap_pair_kernel, dim3(cdiv(total, 128)), dim3(128), 0, (hipStream_t)stream, a);
     rc = check_launch("dataset_ap_update pairs");
     if (rc) return rc;
-    if (t) hipLaunchKernelGGL(ap_match_tp_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a, *t);
+    if (kitti) {
+        ApTpArgs none;
+        memset(&none, 0, sizeof(none));
+        hipLaunchKernelGGL(ap_match_kitti_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a, t ? *t : none, t ? 1 : 0);
+    } else if (t) hipLaunchKernelGGL(ap_match_tp_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a, *t);
     else hipLaunchKernelGGL(ap_match_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
     return check_launch("dataset_ap_update");
 }
@@ -625,7 +871,7 @@ extern "C" int dpft_dataset_ap_update_f32(const float* cls, const float* center,
                                           int64_t* counters, int32_t first_frame, int32_t B, int32_t N, int32_t Mmax,
                                           int32_t C, dpft_stream_t stream) {
     return ap_update(cls, center, size, angle, gt_box, gt_id, counts, iou_thrs, kinds, K, roi6, min_score, scratch, records, capacity,
-                     reserved, counters, first_frame, B, N, Mmax, C, nullptr, stream);
+                     reserved, counters, first_frame, B, N, Mmax, C, nullptr, false, stream);
 }
 
 extern "C" int dpft_dataset_ap_update_tp_f32(const float* cls, const float* center, const float* size, const float* angle,
@@ -638,7 +884,7 @@ extern "C" int dpft_dataset_ap_update_tp_f32(const float* cls, const float* cent
     int rc = ap_fill_tp(t, tp_errors, ref_k, fold_pi, K);
     if (rc) return rc;
     return ap_update(cls, center, size, angle, gt_box, gt_id, counts, iou_thrs, kinds, K, roi6, min_score, scratch, records, capacity,
-                     reserved, counters, first_frame, B, N, Mmax, C, &t, stream);
+                     reserved, counters, first_frame, B, N, Mmax, C, &t, false, stream);
 }
 
 // the two launches of an update with groups; `t` = null: no true-positive errors
@@ -648,7 +894,8 @@ static int ap_update_groups(const float* cls, const float* center, const float* 
                             int64_t* counters, int32_t first_frame, int32_t B, int32_t N, int32_t Mmax, int32_t C,
                             const void* const* desc_ptrs, const int32_t* desc_types, const double* desc_host,
                             const int32_t* axis_cols, const int32_t* axis_counts, const int32_t* axis_values, int32_t n_axes,
-                            void* frames, int64_t frame_capacity, int64_t frames_before, const ApTpArgs* t, dpft_stream_t stream) {
+                            void* frames, int64_t frame_capacity, int64_t frames_before, const ApTpArgs* t, bool kitti,
+                            dpft_stream_t stream) {
     DPFT_REQUIRE(desc_ptrs && desc_types && frames, "dataset_ap_update_groups: null argument");
     DPFT_REQUIRE(n_axes == 0 || (axis_cols && axis_counts && axis_values), "dataset_ap_update_groups: null axis tables");
     ApArgs a;
@@ -693,7 +940,11 @@ static int ap_update_groups(const float* cls, const float* center, const float* 
     hipLaunchKernelGGL(ap_pair_kernel, dim3(cdiv(total, 128)), dim3(128), 0, (hipStream_t)stream, a);
     rc = check_launch("dataset_ap_update_groups pairs");
     if (rc) return rc;
-    if (t) hipLaunchKernelGGL(ap_match_groups_tp_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a, g, *t);
+    if (kitti) {
+        ApTpArgs none;
+        memset(&none, 0, sizeof(none));
+        hipLaunchKernelGGL(ap_match_kitti_groups_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a, g, t ? *t : none, t ? 1 : 0);
+    } else if (t) hipLaunchKernelGGL(ap_match_groups_tp_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a, g, *t);
     else hipLaunchKernelGGL(ap_match_groups_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a, g);
     return check_launch("dataset_ap_update_groups");
 }
@@ -706,7 +957,7 @@ extern "C" int dpft_dataset_ap_update_groups_f32(const float* cls, const float* 
         void* frames, int64_t frame_capacity, int64_t frames_before, dpft_stream_t stream) {
     return ap_update_groups(cls, center, size, angle, gt_box, gt_id, counts, iou_thrs, kinds, K, roi6, min_score, scratch, records,
                             capacity, reserved, counters, first_frame, B, N, Mmax, C, desc_ptrs, desc_types, desc_host, axis_cols,
-                            axis_counts, axis_values, n_axes, frames, frame_capacity, frames_before, nullptr, stream);
+                            axis_counts, axis_values, n_axes, frames, frame_capacity, frames_before, nullptr, false, stream);
 }
 
 extern "C" int dpft_dataset_ap_update_groups_tp_f32(const float* cls, const float* center, const float* size, const float* angle,
@@ -721,7 +972,30 @@ extern "C" int dpft_dataset_ap_update_groups_tp_f32(const float* cls, const floa
     if (rc) return rc;
     return ap_update_groups(cls, center, size, angle, gt_box, gt_id, counts, iou_thrs, kinds, K, roi6, min_score, scratch, records,
                             capacity, reserved, counters, first_frame, B, N, Mmax, C, desc_ptrs, desc_types, desc_host, axis_cols,
-                            axis_counts, axis_values, n_axes, frames, frame_capacity, frames_before, &t, stream);
+                            axis_counts, axis_values, n_axes, frames, frame_capacity, frames_before, &t, false, stream);
+}
+
+// The update with the KITTI walks: frames = null -> without groups (the description and axis arguments are not read), tp_errors =
+// null -> without true-positive errors (ref_k and fold_pi are not read).  The same two launches either way.
+extern "C" int dpft_dataset_ap_update_kitti_f32(const float* cls, const float* center, const float* size, const float* angle,
+        const float* gt_box, const int32_t* gt_id, const int32_t* counts, const double* iou_thrs, const int32_t* kinds, int32_t K,
+        const float* roi6, float min_score, void* scratch, void* records, int64_t capacity, int64_t reserved, int64_t* counters,
+        int32_t first_frame, int32_t B, int32_t N, int32_t Mmax, int32_t C, const void* const* desc_ptrs, const int32_t* desc_types,
+        const double* desc_host, const int32_t* axis_cols, const int32_t* axis_counts, const int32_t* axis_values, int32_t n_axes,
+        void* frames, int64_t frame_capacity, int64_t frames_before, void* tp_errors, int32_t ref_k, int32_t fold_pi,
+        dpft_stream_t stream) {
+    ApTpArgs t;
+    if (tp_errors) {
+        int rc = ap_fill_tp(t, tp_errors, ref_k, fold_pi, K);
+        if (rc) return rc;
+    }
+    if (!frames)
+        return ap_update(cls, center, size, angle, gt_box, gt_id, counts, iou_thrs, kinds, K, roi6, min_score, scratch, records,
+                         capacity, reserved, counters, first_frame, B, N, Mmax, C, tp_errors ? &t : nullptr, true, stream);
+    return ap_update_groups(cls, center, size, angle, gt_box, gt_id, counts, iou_thrs, kinds, K, roi6, min_score, scratch, records,
+                            capacity, reserved, counters, first_frame, B, N, Mmax, C, desc_ptrs, desc_types, desc_host, axis_cols,
+                            axis_counts, axis_values, n_axes, frames, frame_capacity, frames_before, tp_errors ? &t : nullptr, true,
+                            stream);
 }
 
 extern "C" int dpft_dataset_ap_finalize_f64(const void* records_sorted, int64_t n_records, const int64_t* class_start,
@@ -800,4 +1074,54 @@ extern "C" int dpft_dataset_ap_finalize_tp_groups_f64(const void* records_sorted
     DPFT_REQUIRE(record_groups && group_npos, "dataset_ap_finalize_tp_groups: null argument");
     return ap_finalize_tp("dataset_ap_finalize_tp_groups", records_sorted, tp_errors_sorted, record_groups, n_records, class_start,
                           nullptr, group_npos, G, C, ref_k, R, i_min, tp_err, tp_points, stream);
+}
+
+// argument checks and launch shared by the two KITTI finalize entries (record_groups = null: without groups)
+static int ap_finalize_kitti(const char* who, const void* records_sorted, const uint32_t* record_groups, int64_t n_records,
+                             const int64_t* class_start, const int64_t* counters, const double* group_npos, int32_t G, int32_t C,
+                             int32_t K, double* ap40, double* ap11, double* prec, double* rec, double* thresholds, double* tp,
+                             double* fp, int32_t* nthr, dpft_stream_t stream) {
+    DPFT_REQUIRE(records_sorted && class_start && ap40 && ap11 && prec && rec && thresholds && tp && fp && nthr, "%s: null argument",
+                 who);
+    DPFT_REQUIRE(n_records >= 0 && C >= 2 && C <= kApMaxC && K >= 1 && K <= kApMaxK,
+                 "%s: sizes out of range (2 <= C <= %d, 1 <= K <= %d)", who, kApMaxC, kApMaxK);
+    DPFT_REQUIRE(G >= 1 && G <= kApMaxGroups, "%s: 1..%d groups, got %d", who, kApMaxGroups, G);
+    DPFT_REQUIRE(((uintptr_t)records_sorted & 15) == 0, "%s: records need 16-byte alignment", who);
+    ApKittiFinalArgs a;
+    memset(&a, 0, sizeof(a));
+    a.rec = (const int4*)records_sorted; a.rec_groups = record_groups; a.class_start = (const long long*)class_start;
+    a.counters = (const unsigned long long*)counters; a.group_npos = group_npos; a.ap40 = ap40; a.ap11 = ap11; a.prec = prec;
+    a.recall = rec; a.thresholds = thresholds; a.tp = tp; a.fp = fp; a.nthr = nthr; a.n = n_records; a.G = G; a.C = C; a.K = K;
+    hipLaunchKernelGGL(ap_finalize_kitti_kernel, dim3(G * (C - 1) * K), dim3(256), 0, (hipStream_t)stream, a);
+    return check_launch(who);
+}
+
+extern "C" int dpft_dataset_ap_finalize_kitti_f64(const void* records_sorted, int64_t n_records, const int64_t* class_start,
+                                                  const int64_t* counters, int32_t C, int32_t K, double* ap40, double* ap11,
+                                                  double* prec, double* rec, double* thresholds, double* tp, double* fp,
+                                                  int32_t* nthr, dpft_stream_t stream) {
+    DPFT_REQUIRE(counters, "dataset_ap_finalize_kitti: null argument");
+    return ap_finalize_kitti("dataset_ap_finalize_kitti", records_sorted, nullptr, n_records, class_start, counters, nullptr, 1, C, K,
+                             ap40, ap11, prec, rec, thresholds, tp, fp, nthr, stream);
+}
+
+extern "C" int dpft_dataset_ap_finalize_kitti_groups_f64(const void* records_sorted, const uint32_t* record_groups,
+                                                         int64_t n_records, const int64_t* class_start, const double* group_npos,
+                                                         int32_t G, int32_t C, int32_t K, double* ap40, double* ap11, double* prec,
+                                                         double* rec, double* thresholds, double* tp, double* fp, int32_t* nthr,
+                                                         dpft_stream_t stream) {
+    DPFT_REQUIRE(record_groups && group_npos, "dataset_ap_finalize_kitti_groups: null argument");
+    return ap_finalize_kitti("dataset_ap_finalize_kitti_groups", records_sorted, record_groups, n_records, class_start, nullptr,
+                             group_npos, G, C, K, ap40, ap11, prec, rec, thresholds, tp, fp, nthr, stream);
+}
+
+// The host side of ap_kitti_ranks, for the tests: the same function the finalize kernel runs, no GPU involved.
+extern "C" int dpft_dataset_ap_kitti_ranks(int64_t n1, int64_t npos, int64_t* ranks) {
+    DPFT_REQUIRE(ranks, "dataset_ap_kitti_ranks: null argument");
+    DPFT_REQUIRE(n1 >= 0 && npos >= 1 && n1 <= npos, "dataset_ap_kitti_ranks: 0 <= n1 <= npos and npos >= 1, got %lld and %lld",
+                 (long long)n1, (long long)npos);
+    long long picked[kApKittiPoints];
+    const int nt = ap_kitti_ranks(n1, npos, picked);
+    for (int t = 0; t < nt; ++t) ranks[t] = picked[t];
+    return nt;
 }

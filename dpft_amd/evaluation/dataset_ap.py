@@ -5,7 +5,8 @@ quantity of the K-Radar table instead -- one precision/recall curve per class ov
 
 NOT K-Radar's evaluation tool: that one follows KITTI's target-major two-pass protocol (difficulty levels, don't-care regions,
 score thresholds chosen from the recall positions); this is the detection-major VOC order stated below.  The numbers are not
-interchangeable with published ones: the export path (exporters/kradar.py) stays the way to official numbers.
+interchangeable with published ones: the export path (exporters/kradar.py) stays the way to official numbers.  ``kitti: true`` adds
+a second table that follows that protocol for what the exporter writes ("KITTI protocol" below); the table here does not change.
 
 Definition (tests/dataset_ap_ref.py restates it line by line in numpy fp64).  A combination is (IoU kind, threshold); there
 are K = len(kinds) * len(iou) of them, kinds outermost.
@@ -71,6 +72,68 @@ Device side with ``tp_errors``: ``dpft_dataset_ap_update_tp_f32`` / ``_groups_tp
 launches; the wave that owns the reference combination keeps the target it took, and the append loop writes one row of four
 int64 into a second store at the record's position (zeros for a non-TP).  ``dpft_dataset_ap_finalize_tp_f64`` / ``_tp_groups_f64``
 (one launch) runs beside the finalize entry on the error rows gathered by the records' sort permutation.
+
+KITTI protocol (``kitti``; tests/dataset_ap_kitti_ref.py restates it literally with plain loops).  The table of KITTI's evaluation
+tool, which K-Radar's tool follows, from the same accumulation and beside the table above.  NOT verified: K-Radar's tool is not
+available to this project, equality with its output on a real export has not been checked, and the collapse of the difficulty
+levels is argued from the exporter's constants, not observed.
+
+* Shared with the table above: detections, ground truth, roi, ``min_score``, NaN handling, box geometry, both IoU kinds, the
+  strict ``IoU > threshold`` rule, and npos[c].
+* Detection order: a frame's detection order (its "file order") is ascending query index -- the exporter writes objects in query
+  order.
+* Difficulty levels and don't-care regions collapse: the exporter writes truncation 0, occlusion 0 and the 2-D box 50 50 150 150
+  for every object, so every target is valid at every level and no detection is ever "ignored".  One table, not three.  The
+  pass-2 reduction below DEPENDS on this: with ignored detections (don't-care areas, neighbouring classes) it does not hold.
+* Pass 1, per frame, class and combination: targets in ascending index; each takes, among the detections of its class that are
+  still unassigned and have IoU > thr, the one with the highest score (ties: lower query).  The tool runs this pass with score
+  threshold 0.0: a detection with score < 0 takes no part (reachable only with a negative ``min_score``).  The taken detection is
+  a pass-1 TP.
+* Thresholds, per class and combination, from all pass-1 TP scores of the split in descending order (n1 of them), G = npos[c], in
+  fp64 operation for operation as the tool does it::
+
+      cur = 0.0
+      for i in 0..n1-1:
+          l = (i+1)/G
+          r = (i+2)/G if i < n1-1 else l
+          if (r - cur) < (cur - l) and i < n1-1: continue
+          take score[i]
+          cur += 1/40.0
+
+  At most 41 thresholds.
+* Pass 2, per threshold s: the active detections are those with score >= s.  Per frame, targets in ascending index; each takes,
+  among the active unassigned detections of its class with IoU > thr, the one with the largest IoU (ties: lower query).  TP(s) =
+  matched targets, FP(s) = active detections of the class that were not matched, FN(s) = G - TP(s).
+* Table: prec[i] = TP / (TP + FP) and rec[i] = TP / G at threshold i, prec[i] = 0 for i at or beyond the number of thresholds;
+  then the suffix maximum over i; ``AP`` (R40) = (prec[1] + .. + prec[40]) / 40, ``AP11`` = (prec[0] + prec[4] + .. + prec[40]) / 11,
+  both summed in ascending i -- the tool's vintage decides which of the two a paper used.  npos = 0 gives NaN, targets without a
+  TP give 0; mAP = mean over the classes with npos > 0.
+* Keys: ``kitti/AP_{kind}@{iou}/{c}``, ``kitti/AP11_{kind}@{iou}/{c}``, ``kitti/mAP_{kind}@{iou}``, ``kitti/mAP11_{kind}@{iou}`` (with
+  groups the same four per group with the AP keys' suffix) and the fp64 tensors ``kitti_ap``, ``kitti_ap11`` (C-1, K),
+  ``kitti_prec`` (before the suffix maximum), ``kitti_rec``, ``kitti_thresholds`` (NaN-padded), ``kitti_tp``, ``kitti_fp``
+  (C-1, K, 41), ``kitti_nthr`` (C-1, K) int32; with groups ``group_kitti_ap`` and ``group_kitti_ap11`` (G, C-1, K).
+* True-positive errors stay on the VOC matching of the table above.
+
+The two reductions of the device path (the reference file does NOT use them; tests/test_dataset_ap_kitti_ref.py compares the two
+on random frames with ties in score and IoU):
+
+1. Pass-1 bit: the pass-1 TP of target i is the first still-unassigned detection, in (score desc, query asc) order, with
+   IoU > thr and score >= 0.
+2. Pass-2 bit: insert the frame's detections one by one in (score desc, query asc) order into a maintained matching.  The
+   entering detection x is offered to the targets in ascending index from start = 0 and goes to the first target t with
+   IoU(x, t) > thr that is unmatched, or holds a smaller IoU, or holds an equal IoU from a higher query.  If t was unmatched the
+   detection being INSERTED gets its bit and the insertion ends; otherwise the displaced detection becomes x, start = t + 1, and
+   the offer goes on; if no target takes x no bit is set.  At most M steps.  Then for every s, TP(s) = the pass-2 bits of the
+   detections with score >= s and FP(s) = their number minus TP(s): inside a group of equal scores the single bits depend on the
+   insertion order, their sum does not, and a threshold always takes a whole tie group.
+
+So the protocol over the split is two prefix sums over a class's records in the order they are sorted into anyway.  Device side
+with ``kitti``: ``dpft_dataset_ap_update_kitti_f32`` instead of the update entries (groups and tp_errors by nullable arguments) --
+the SAME two launches; after its own walk the wave that owns a combination does the two KITTI walks and the bits go into bits
+8..15 (pass 1) and 16..23 (pass 2) of the record's fourth word, bits 0..7 stay the TP bits.  The record stays 16 bytes; store,
+capacity rule, cursor atomic, counters, ``state()``, ``merge`` and ``all_gather`` are untouched: the bits travel with the records.
+``dpft_dataset_ap_finalize_kitti_f64`` / ``_kitti_groups_f64`` (one launch) runs beside the finalize entry on the same sorted
+records; a group's table has the bits of an ungrouped run over its frames (its own npos, its own thresholds).
 """
 from __future__ import annotations
 
@@ -81,6 +144,7 @@ from typing import Any, Dict, List, Optional, Sequence
 import torch
 
 KINDS = ("bev", "3d")
+KITTI_POINTS = 41                                    # sample points of the KITTI-protocol table (csrc/ap_kitti.h)
 DEFAULT_ROI = (0.0, 72.0, -6.4, 6.4, -2.0, 6.0)      # the exporter's field of view (csrc/export.hip)
 MAX_COMBINATIONS = 8
 N_COUNTERS = 32
@@ -200,13 +264,14 @@ class DatasetAP:
     def __init__(self, num_classes: int, iou: Sequence[float] = (0.3, 0.5, 0.7), kinds: Sequence[str] = KINDS,
                  recall_points: int = 40, min_score: float = 0.0, roi: Any = _DEFAULT, initial_capacity: int = 1 << 16,
                  groups: Any = None, mappings: Optional[Dict[str, Any]] = None, initial_frame_capacity: int = 1 << 10,
-                 tp_errors: Any = None):
+                 tp_errors: Any = None, kitti: bool = False):
         """``roi``: [xmin, xmax, ymin, ymax, zmin, zmax] (strict inequalities) or None for no filter; default = the exporter's
         box.  ``initial_capacity``: records the store holds before it first doubles.  ``groups``: None, True (all axes) or a
         list out of "time", "road", "weather" -- one more table per scene-description subset; ``mappings``: the exporter's
         name -> value dicts under "time_zone" / "road_structures" / "weather_conditions" (None = its defaults);
         ``initial_frame_capacity``: frames the frame store holds before it first doubles.  ``tp_errors``: None, True or a dict of
-        at / min_recall / angle_period -- the true-positive errors of one reference combination beside the AP."""
+        at / min_recall / angle_period -- the true-positive errors of one reference combination beside the AP.  ``kitti``:
+        True adds the KITTI-protocol table (the ``kitti/`` keys) beside the VOC-order one."""
         if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 2 <= num_classes <= 16:
             raise ValueError(f"dataset_ap: num_classes must be 2..16 (background + classes), got {num_classes!r}")
         iou = [iou] if isinstance(iou, (int, float)) and not isinstance(iou, bool) else iou
@@ -242,6 +307,11 @@ class DatasetAP:
         self.combinations = [(k, t) for k in self.kinds for t in self.iou]
         self.initial_capacity = initial_capacity
         self.tp = _parse_tp_errors(tp_errors, self.combinations, self.kinds, self.iou, recall_points)
+        if kitti is None:
+            kitti = False
+        if not isinstance(kitti, bool):
+            raise ValueError(f"dataset_ap: 'kitti' must be true or false, got {kitti!r}")
+        self.kitti = kitti
         if isinstance(initial_frame_capacity, bool) or not isinstance(initial_frame_capacity, int) or initial_frame_capacity < 1:
             raise ValueError(f"dataset_ap: initial_frame_capacity must be a positive integer, got {initial_frame_capacity!r}")
         self.initial_frame_capacity = initial_frame_capacity
@@ -256,7 +326,7 @@ class DatasetAP:
     @classmethod
     def from_config(cls, config: Dict[str, Any]) -> Optional["DatasetAP"]:
         """``config['evaluate']['dataset_ap']``: true (defaults) or a dict of iou / kinds / recall_points / min_score / roi /
-        groups / tp_errors.  Absent or false -> None.  The class count comes from ``config['model']['head']['num_classes']``; with
+        groups / tp_errors / kitti.  Absent or false -> None.  The class count comes from ``config['model']['head']['num_classes']``; with
         ``groups`` (true, or a list out of "time", "road", "weather") the group names come from ``config['data']`` the way the
         exporter reads them (time_zone / road_structures / weather_conditions, absent = its defaults)."""
         spec = config.get("evaluate", {}).get("dataset_ap")
@@ -266,10 +336,10 @@ class DatasetAP:
             spec = {}
         if not isinstance(spec, dict):
             raise ValueError(f"evaluate.dataset_ap must be true or a dict, got {spec!r}")
-        unknown = sorted(set(spec) - {"iou", "kinds", "recall_points", "min_score", "roi", "groups", "tp_errors"})
+        unknown = sorted(set(spec) - {"iou", "kinds", "recall_points", "min_score", "roi", "groups", "tp_errors", "kitti"})
         if unknown:
             raise ValueError(f"evaluate.dataset_ap: unknown key(s) {unknown} (iou, kinds, recall_points, min_score, roi, groups, "
-                             f"tp_errors)")
+                             f"tp_errors, kitti)")
         try:
             ncls = config["model"]["head"]["num_classes"]
         except (KeyError, TypeError):
@@ -393,7 +463,10 @@ class DatasetAP:
                 counts_t.data_ptr(), thr, kinds, K, roi, self.min_score, scratch.data_ptr(), self._records.data_ptr(),
                 self.capacity, self._bound, self._counters.data_ptr(), int(first_frame), B, N, Mmax, ncls)
         tp = () if self.tp is None else (self._tp_rows.data_ptr(), self.tp["k"], int(self.tp["angle_period"] == "pi"))
-        if not self.axes:
+        if self.kitti and not self.axes:       # one entry for every mix of groups and tp_errors: a null pointer switches each off
+            lib.call("dpft_dataset_ap_update_kitti_f32", *args, None, None, None, None, None, None, 0, None, 0, 0,
+                     *(tp or (None, 0, 0)), stream())
+        elif not self.axes:
             lib.call("dpft_dataset_ap_update_tp_f32" if tp else "dpft_dataset_ap_update_f32", *args, *tp, stream())
         else:
             ptrs, types, host, _keep = self._descriptions(labels, dev)
@@ -405,8 +478,12 @@ class DatasetAP:
             for s, a in enumerate(self.axes):
                 for i, (v, _) in enumerate(self.axis_tables[a]):
                     vals[s * MAX_AXIS_VALUES + i] = v
-            lib.call("dpft_dataset_ap_update_groups_tp_f32" if tp else "dpft_dataset_ap_update_groups_f32", *args, ptrs, types,
-                     host, cols, cnts, vals, n_axes, self._frames.data_ptr(), self.frame_capacity, self._nframes, *tp, stream())
+            group_args = (ptrs, types, host, cols, cnts, vals, n_axes, self._frames.data_ptr(), self.frame_capacity, self._nframes)
+            if self.kitti:
+                lib.call("dpft_dataset_ap_update_kitti_f32", *args, *group_args, *(tp or (None, 0, 0)), stream())
+            else:
+                lib.call("dpft_dataset_ap_update_groups_tp_f32" if tp else "dpft_dataset_ap_update_groups_f32", *args, *group_args,
+                         *tp, stream())
             self._nframes += B
         self._bound += B * N
 
@@ -415,7 +492,8 @@ class DatasetAP:
         the int64 ``counters`` ([0] = n, [1] dropped_nan, [16 + c] npos of class c).  Reads the cursor (a sync).  With groups
         also ``frames`` (F, 18) int32 = frame, group bitmask, npos of classes 0..15 of every frame seen (in arbitrary order).  With
         ``tp_errors`` also ``tp_errors`` (n, 4) int64 parallel to ``records`` = ate, aze, ase, aoe of a TP of the reference
-        combination as rint(e * 2^32), zeros otherwise (counters[3] = errors that did not fit)."""
+        combination as rint(e * 2^32), zeros otherwise (counters[3] = errors that did not fit).  With ``kitti`` the records' fourth
+        word also holds the pass-1 bits (8..15) and the pass-2 bits (16..23) of the KITTI protocol."""
         if self._counters is None:
             st = {"records": torch.empty((0, 4), dtype=torch.int32), "counters": torch.zeros(N_COUNTERS, dtype=torch.int64)}
             if self.axes:
@@ -469,8 +547,9 @@ class DatasetAP:
     def merge(self, other: "DatasetAP") -> None:
         """Concatenates the record stores (with groups also the frame stores, with tp_errors also the error rows) and adds the
         counters (the frames of the two must not overlap)."""
-        if (other.combinations, other.num_classes, other.recall_points, other.group_names, other.axis_tables, other.tp) != \
-                (self.combinations, self.num_classes, self.recall_points, self.group_names, self.axis_tables, self.tp):
+        if (other.combinations, other.num_classes, other.recall_points, other.group_names, other.axis_tables, other.tp,
+                other.kitti) != (self.combinations, self.num_classes, self.recall_points, self.group_names, self.axis_tables,
+                                 self.tp, self.kitti):
             raise ValueError("DatasetAP.merge: the two accumulators differ in their parameters")
         a, b = self.state(), other.state()
         if not b["records"].is_cuda:
@@ -533,20 +612,25 @@ class DatasetAP:
         without a group are then the ``all`` group's.  With ``tp_errors`` also ``ATE/{c}``, ``AZE/{c}``, ``ASE/{c}``,
         ``AOE/{c}``, ``mATE`` .. ``mAOE``, ``tp_points/{c}`` (with the group suffix of the AP keys), ``tp_saturated`` and the fp64
         tensors ``tp_err`` (C-1, 4), ``tp_points`` (C-1), with groups ``group_tp_err`` (G, C-1, 4) and ``group_tp_points``
-        (G, C-1); every TP-error value is NaN when ``tp_saturated`` is not zero."""
+        (G, C-1); every TP-error value is NaN when ``tp_saturated`` is not zero.  With ``kitti`` also the ``kitti/`` scalars and the
+        ``kitti_*`` tensors of the module docstring's "KITTI protocol" (one more launch, on the same sorted records)."""
         from dpft_amd.hip.lib import lib, stream
         Cn, K = self.num_classes, len(self.combinations)
         groups = None
         tp_err, tp_points = torch.full((Cn - 1, 4), float("nan"), dtype=torch.float64), torch.zeros(Cn - 1, dtype=torch.float64)
         saturated = 0
+        kitti = None
         if self.axes:
             groups = self._compute_groups()
+            kitti = groups.pop("kitti", None)
             ap, tp, npos, dropped = groups["group_ap"][0], groups["group_tp"][0], groups["group_npos"][0], groups.pop("dropped")
             if self.tp is not None:
                 tp_err, tp_points, saturated = groups["group_tp_err"][0], groups["group_tp_points"][0], groups.pop("saturated")
         elif self._counters is None:
             ap = torch.full((Cn - 1, K), float("nan"), dtype=torch.float64)
             npos, tp, dropped = torch.zeros(Cn - 1, dtype=torch.float64), torch.zeros((Cn - 1, K), dtype=torch.float64), 0
+            if self.kitti:
+                kitti = self._kitti_finalize(None, 0, None, None)
         else:
             st = self.state()
             dev = st["counters"].device
@@ -567,6 +651,8 @@ class DatasetAP:
                 lib.call("dpft_dataset_ap_finalize_tp_f64", rec.data_ptr(), rows.data_ptr(), n, start.data_ptr(),
                          st["counters"].data_ptr(), Cn, self.tp["k"], self.recall_points, self.tp["i_min"], out[base:].data_ptr(),
                          out[base + (Cn - 1) * 4:].data_ptr(), stream())
+            if self.kitti:               # one more launch over the same sorted records
+                kitti = self._kitti_finalize(rec, n, start, st["counters"])
             host = out.cpu()
             ap, tp = host[:(Cn - 1) * K].reshape(Cn - 1, K), host[(Cn - 1) * K:2 * (Cn - 1) * K].reshape(Cn - 1, K)
             npos = host[2 * (Cn - 1) * K:base]
@@ -592,6 +678,10 @@ class DatasetAP:
             self._tp_keys(res, tp_err.tolist(), tp_points.tolist(), "")
             res["tp_saturated"] = float(saturated)
             res["tp_err"], res["tp_points"] = tp_err, tp_points
+        if kitti is not None:            # [0] = the only table, or the ``all`` group's
+            self._kitti_keys(res, kitti["ap"][0].tolist(), kitti["ap11"][0].tolist(), npos.tolist(), "")
+            for k, v in kitti.items():
+                res[f"kitti_{k}"] = v[0]
         if groups is not None:
             all_ap, all_npos, all_nframes = (groups[k].tolist() for k in ("group_ap", "group_npos", "group_nframes"))
             for g, gname in enumerate(self.group_names[1:], 1):      # (plain lists: ~800 reads of a host tensor cost milliseconds)
@@ -611,10 +701,58 @@ class DatasetAP:
                 all_err, all_points = groups["group_tp_err"].tolist(), groups["group_tp_points"].tolist()
                 for g, gname in enumerate(self.group_names[1:], 1):
                     self._tp_keys(res, all_err[g], all_points[g], "/" + gname)
+            if kitti is not None:
+                all_kap, all_kap11 = kitti["ap"].tolist(), kitti["ap11"].tolist()
+                for g, gname in enumerate(self.group_names[1:], 1):
+                    self._kitti_keys(res, all_kap[g], all_kap11[g], all_npos[g], "/" + gname)
+                res["group_kitti_ap"], res["group_kitti_ap11"] = kitti["ap"], kitti["ap11"]
             res["bad_description"] = float(groups.pop("bad"))
             res.update(groups)
             res["group_names"] = list(self.group_names)
         return res
+
+    def _kitti_finalize(self, rec: Optional[torch.Tensor], n: int, start: Optional[torch.Tensor], counters: Optional[torch.Tensor],
+                        rec_groups: Optional[torch.Tensor] = None, group_npos: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """The KITTI-protocol table of the sorted records (``rec`` None: nothing accumulated) as host tensors with a leading
+        group axis: ap, ap11 (G, C-1, K), prec, rec, thresholds, tp, fp (G, C-1, K, 41), nthr (G, C-1, K) int32.  One launch
+        (``dpft_dataset_ap_finalize_kitti_f64`` or ``_groups_f64`` with the group masks and the group npos on the device)."""
+        from dpft_amd.hip.lib import lib, stream
+        Cn, K, G = self.num_classes, len(self.combinations), max(len(self.group_names), 1)
+        cells = G * (Cn - 1) * K
+        names, sizes = ("ap", "ap11", "prec", "rec", "thresholds", "tp", "fp"), (1, 1) + (KITTI_POINTS,) * 5
+        if rec is None:
+            out = {k: torch.zeros((G, Cn - 1, K) + ((w,) if w > 1 else ()), dtype=torch.float64) for k, w in zip(names, sizes)}
+            for k in ("ap", "ap11", "thresholds"):
+                out[k].fill_(float("nan"))
+            out["nthr"] = torch.zeros((G, Cn - 1, K), dtype=torch.int32)
+            return out
+        dev = rec.device
+        buf = torch.empty(cells * sum(sizes), dtype=torch.float64, device=dev)
+        nthr = torch.empty(cells, dtype=torch.int32, device=dev)
+        offs = [cells * sum(sizes[:i]) for i in range(len(sizes))]
+        ptrs = [buf[o:].data_ptr() for o in offs]
+        if rec_groups is None:
+            lib.call("dpft_dataset_ap_finalize_kitti_f64", rec.data_ptr(), n, start.data_ptr(), counters.data_ptr(), Cn, K, *ptrs,
+                     nthr.data_ptr(), stream())
+        else:
+            lib.call("dpft_dataset_ap_finalize_kitti_groups_f64", rec.data_ptr(), rec_groups.data_ptr(), n, start.data_ptr(),
+                     group_npos.data_ptr(), G, Cn, K, *ptrs, nthr.data_ptr(), stream())
+        host = buf.cpu()
+        out = {k: host[o:o + cells * w].reshape((G, Cn - 1, K) + ((w,) if w > 1 else ())) for k, w, o in zip(names, sizes, offs)}
+        out["nthr"] = nthr.cpu().reshape(G, Cn - 1, K)
+        return out
+
+    def _kitti_keys(self, res: Dict[str, Any], ap: List[List[float]], ap11: List[List[float]], npos: List[float], tail: str) -> None:
+        """The KITTI scalars of one table (``tail`` = the group suffix): AP (R40) and AP11 per class and combination, and their
+        means over the classes with ground truth."""
+        Cn = self.num_classes
+        for k, (kind, thr) in enumerate(self.combinations):
+            name = self.key(kind, thr)
+            for label, table in (("AP", ap), ("AP11", ap11)):
+                vals = [table[c][k] for c in range(Cn - 1) if npos[c] > 0]
+                for c in range(1, Cn):
+                    res[f"kitti/{label}_{name}/{c}{tail}"] = table[c - 1][k]
+                res[f"kitti/m{label}_{name}{tail}"] = sum(vals) / len(vals) if vals else float("nan")
 
     def _tp_keys(self, res: Dict[str, Any], err: List[List[float]], points: List[float], tail: str) -> None:
         """The TP-error scalars of one table (``tail`` = the group suffix): per class, and the mean over the classes that are not
@@ -644,6 +782,7 @@ class DatasetAP:
                 host = torch.cat([host, torch.full((sizes[5],), float("nan"), dtype=torch.float64),
                                   torch.zeros(sizes[6], dtype=torch.float64)])
             dropped = 0
+            kitti = self._kitti_finalize(None, 0, None, None) if self.kitti else None
         else:
             st = self.state()
             dev = st["counters"].device
@@ -677,6 +816,8 @@ class DatasetAP:
                 lib.call("dpft_dataset_ap_finalize_tp_groups_f64", rec.data_ptr(), rows.data_ptr(), rec_groups.data_ptr(), n,
                          start.data_ptr(), out[o[2]:].data_ptr(), G, Cn, self.tp["k"], self.recall_points, self.tp["i_min"],
                          out[o[5]:].data_ptr(), out[o[6]:].data_ptr(), stream())
+            # (after the grouped finalize on the same stream, like the TP errors: it reads the npos that one wrote)
+            kitti = self._kitti_finalize(rec, n, start, None, rec_groups, out[o[2]:]) if self.kitti else None
             host = out.cpu()
             counters = st["counters"].cpu()
             dropped, saturated = int(counters[DROPPED_NAN]), int(counters[TP_SATURATED])
@@ -686,6 +827,8 @@ class DatasetAP:
         if self.tp is not None:
             err, points = torch.split(host, sizes)[5:]
             res.update(group_tp_err=err.reshape(G, Cn - 1, 4), group_tp_points=points.reshape(G, Cn - 1), saturated=saturated)
+        if kitti is not None:
+            res["kitti"] = kitti
         return res
 
     def scalars(self) -> Dict[str, float]:

@@ -272,6 +272,11 @@ SIGNATURES = {
                                              [_I, _P, _L, _L, _P, _I, _I, _P]),
     "dpft_dataset_ap_finalize_tp_f64": (_I, [_P, _P, _L, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "dpft_dataset_ap_finalize_tp_groups_f64": (_I, [_P, _P, _P, _L, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "dpft_dataset_ap_update_kitti_f32": (_I, [_P] * 9 + [_I, _P, _F, _P, _P, _L, _L, _P, _I, _I, _I, _I, _I] + [_P] * 6 +
+                                         [_I, _P, _L, _L, _P, _I, _I, _P]),
+    "dpft_dataset_ap_finalize_kitti_f64": (_I, [_P, _L, _P, _P, _I, _I] + [_P] * 9),
+    "dpft_dataset_ap_kitti_ranks": (_I, [_L, _L, _P]),
+    "dpft_dataset_ap_finalize_kitti_groups_f64": (_I, [_P, _P, _L, _P, _P, _I, _I, _I] + [_P] * 9),
     "dpft_nms_scratch_bytes": (_L, [_I, _I]),
     "dpft_nms_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "dpft_tta_scratch_bytes": (_L, [_I, _I, _I]),

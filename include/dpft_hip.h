@@ -1157,6 +1157,54 @@ int dpft_dataset_ap_finalize_tp_groups_f64(const void* records_sorted, const int
                                            int32_t i_min, double* tp_err, double* tp_points, dpft_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * KITTI-protocol table beside the split-level AP (evaluate.dataset_ap.kitti; dpft_amd/evaluation/dataset_ap.py states
+ * the protocol -- target-major two-pass matching, <= 41 score thresholds per class and combination -- and the two
+ * one-bit reductions used here; one difficulty level, no don't-care regions, no neighbouring classes).
+ * update_kitti: dpft_dataset_ap_update_f32 (same two launches, records, counters and capacity rule) whose match pass
+ *   also sets, in the record's fourth word, bit 8 + k = pass-1 TP of combination k (targets in ascending index each take
+ *   the first unassigned detection in (score desc, query asc) order with IoU > threshold and score >= 0) and bit 16 + k =
+ *   pass-2 bit (the detections inserted in that order into a target-major largest-IoU matching, ties to the lower
+ *   query; set when the insertion adds a matched target).  Bits 0..7 stay the TP bits of dpft_dataset_ap_update_f32.
+ *   frames = NULL: without groups (desc_*, axis_*, n_axes, frame_capacity, frames_before are not read); otherwise the
+ *   frame rows of dpft_dataset_ap_update_groups_f32.  tp_errors = NULL: without true-positive errors (ref_k, fold_pi are
+ *   not read); otherwise the error rows of dpft_dataset_ap_update_tp_f32 (on the VOC matching of bits 0..7).
+ * finalize_kitti: records_sorted / class_start / counters as dpft_dataset_ap_finalize_f64 takes them.  One workgroup per
+ *   (class, combination): n1 = pass-1 bits, G = npos; the thresholds are the scores of the pass-1 TPs (descending) at the
+ *   ranks the tool's fp64 sampling loop picks (cur = 0; rank i is skipped while (i + 2) / G - cur < cur - (i + 1) / G and
+ *   i < n1 - 1; cur += 1 / 40.0 per pick); at threshold s, A = records with score >= s, tp = pass-2 bits among them,
+ *   fp = A - tp, prec = tp / A, rec = tp / G.  Outputs fp64: prec, rec, tp, fp (C-1,K,41; zeros from nthr on),
+ *   thresholds (C-1,K,41; NaN from nthr on), ap40 (C-1,K) = mean of the suffix maximum of prec at i = 1..40, ap11 = the
+ *   same at i = 0, 4, .., 40 (NaN for a class without ground truth); nthr (C-1,K) int32.
+ * finalize_kitti_groups: the same per (group, class, combination) over the member records (record_groups as
+ *   dpft_dataset_ap_finalize_groups_f64 takes it) with the group's own ground truth group_npos (G,C-1, device: the npos
+ *   finalize_groups wrote) and its own thresholds; every output gains a leading G: the bits of an ungrouped run over the
+ *   group's frames.
+ * ---------------------------------------------------------------------------------------- */
+int dpft_dataset_ap_update_kitti_f32(const float* cls, const float* center, const float* size, const float* angle,
+                                     const float* gt_box, const int32_t* gt_id, const int32_t* counts,
+                                     const double* iou_thrs, const int32_t* kinds, int32_t K, const float* roi6,
+                                     float min_score, void* scratch, void* records, int64_t capacity, int64_t reserved,
+                                     int64_t* counters, int32_t first_frame, int32_t B, int32_t N, int32_t Mmax,
+                                     int32_t C, const void* const* desc_ptrs, const int32_t* desc_types,
+                                     const double* desc_host, const int32_t* axis_cols, const int32_t* axis_counts,
+                                     const int32_t* axis_values, int32_t n_axes, void* frames, int64_t frame_capacity,
+                                     int64_t frames_before, void* tp_errors, int32_t ref_k, int32_t fold_pi,
+                                     dpft_stream_t stream);
+int dpft_dataset_ap_finalize_kitti_f64(const void* records_sorted, int64_t n_records, const int64_t* class_start,
+                                       const int64_t* counters, int32_t C, int32_t K, double* ap40, double* ap11,
+                                       double* prec, double* rec, double* thresholds, double* tp, double* fp,
+                                       int32_t* nthr, dpft_stream_t stream);
+/* HOST only (no launch): the ranks, among the n1 pass-1 TP scores in descending order, that finalize_kitti picks as
+ * thresholds for npos ground-truth boxes (0 <= n1 <= npos, npos >= 1) into ranks (HOST, room for 41); returns their
+ * number, 0..41, or a negative error code.  The function the kernel runs (csrc/ap_kitti.h), for tests. */
+int dpft_dataset_ap_kitti_ranks(int64_t n1, int64_t npos, int64_t* ranks);
+int dpft_dataset_ap_finalize_kitti_groups_f64(const void* records_sorted, const uint32_t* record_groups,
+                                              int64_t n_records, const int64_t* class_start, const double* group_npos,
+                                              int32_t G, int32_t C, int32_t K, double* ap40, double* ap11, double* prec,
+                                              double* rec, double* thresholds, double* tp, double* fp, int32_t* nthr,
+                                              dpft_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Rotated-box NMS between the model and its consumers (dpft_amd/evaluation/nms.py states the definition; the reference
  * has no such step).  Three launches on `stream`, no read-back, no floating-point atomics: the same input gives the
  * same bits.  Per sample: candidates = queries with argmax class c != 0 (first maximum, NaN = maximum) and a non-NaN

@@ -20,9 +20,16 @@ key in the same process:
    side show the run-to-run spread that a difference has to exceed; and the update entries alone on pre-packed targets.
 6. ``DatasetAP.compute()`` on about 2 * 10^5 records with and without the key, and the two finalize entries alone.
 
+With ``--kitti`` the KITTI-protocol table's leg instead (evaluate.dataset_ap.kitti), every figure beside the run without the key
+in the same process:
+
+7. ``DatasetAP.update`` with and without the key on the same tensors, measured twice each (a, b, a, b), and the update entries
+   alone on pre-packed targets.
+8. ``DatasetAP.compute()`` on about 2 * 10^5 records with and without the key, and the two finalize entries alone.
+
 Prints JSON lines and writes them to ``--out`` (default profiles/dataset_ap.txt, with ``--groups`` profiles/dataset_ap_groups.txt,
-with ``--tp-errors`` profiles/dataset_ap_tp.txt).
-Usage: python tools/dataset_ap_cost.py [--groups | --tp-errors] [--reps 200] [--records 200000] [--out FILE]"""
+with ``--tp-errors`` profiles/dataset_ap_tp.txt, with ``--kitti`` profiles/dataset_ap_kitti.txt).
+Usage: python tools/dataset_ap_cost.py [--groups | --tp-errors | --kitti] [--reps 200] [--records 200000] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -42,12 +49,14 @@ def main():
     p.add_argument("--records", type=int, default=200000)
     p.add_argument("--groups", action="store_true", help="the groups leg (3., 4.) instead of 1. and 2.")
     p.add_argument("--tp-errors", action="store_true", help="the true-positive errors' leg (5., 6.) instead of 1. and 2.")
+    p.add_argument("--kitti", action="store_true", help="the KITTI-protocol table's leg (7., 8.) instead of 1. and 2.")
     p.add_argument("--out", default=None)
     args = p.parse_args()
-    if args.groups and args.tp_errors:
-        p.error("--groups and --tp-errors are separate legs")
+    if args.groups + args.tp_errors + args.kitti > 1:
+        p.error("--groups, --tp-errors and --kitti are separate legs")
     if args.out is None:
-        name = "dataset_ap_groups.txt" if args.groups else "dataset_ap_tp.txt" if args.tp_errors else "dataset_ap.txt"
+        name = "dataset_ap_groups.txt" if args.groups else "dataset_ap_tp.txt" if args.tp_errors else \
+            "dataset_ap_kitti.txt" if args.kitti else "dataset_ap.txt"
         args.out = os.path.join(ROOT, "profiles", name)
     import numpy as np
     import torch
@@ -94,6 +103,12 @@ def main():
 
     if args.tp_errors:
         tp_leg(args, torch, DatasetAP, KINDS, pack_targets, lib, stream, dev, out, labels, B, N, Cn, timed, emit)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
+
+    if args.kitti:
+        kitti_leg(args, torch, DatasetAP, KINDS, pack_targets, lib, stream, dev, out, labels, B, N, Cn, timed, emit)
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")
         return
@@ -339,6 +354,109 @@ def tp_leg(args, torch, DatasetAP, KINDS, pack_targets, lib, stream, dev, out, l
           "dpft_dataset_ap_finalize_tp_f64 alone (one workgroup per class)": timed(finalize_tp),
           "gather of the error rows by the sort permutation": timed(lambda: st["tp_errors"][perm].contiguous()),
           "mATE": res["mATE"], "mAZE": res["mAZE"], "mASE": res["mASE"], "mAOE": res["mAOE"], "tp_saturated": res["tp_saturated"]})
+
+
+def kitti_leg(args, torch, DatasetAP, KINDS, pack_targets, lib, stream, dev, out, labels, B, N, Cn, timed, emit):
+    """7. and 8. of the module docstring: an accumulator with the key and one without, fed the same batches in the same process."""
+    plain, kitti = DatasetAP(Cn, initial_capacity=1 << 22), DatasetAP(Cn, initial_capacity=1 << 22, kitti=True)
+    frame = {"plain": 0, "kitti": 0}
+
+    def update(ap, key):
+        def fn():
+            ap.update(out, labels, frame[key])
+            frame[key] += B
+        return fn
+
+    kitti.update(out, labels, 0)
+    st = kitti.state()
+    K = len(plain.combinations)
+    n_det = int(st["counters"][0])
+    n_p1 = [int(((st["records"][:, 3] >> (8 + k)) & 1).sum()) for k in range(K)]
+    n_p2 = [int(((st["records"][:, 3] >> (16 + k)) & 1).sum()) for k in range(K)]
+    kitti.reset()
+    t_plain, t_kitti = [], []
+    for _ in range(2):                                          # a, b, a, b: the spread of one side beside the difference
+        t_plain.append(timed(update(plain, "plain")))
+        t_kitti.append(timed(update(kitti, "kitti")))
+
+    # the entries alone, on pre-packed targets
+    counts = [int(l["gt_class"].shape[0]) for l in labels]
+    gt_box, _, gt_id, counts_t, Mmax = pack_targets(labels, counts, Cn, dev)
+    thr = (C.c_double * K)(*[t for _, t in plain.combinations])
+    kinds = (C.c_int32 * K)(*[KINDS.index(k) for k, _ in plain.combinations])
+    roi = (C.c_float * 6)(*plain.roi)
+    scratch = torch.empty(int(lib.dpft_dataset_ap_scratch_bytes(B, N, Mmax)) // 8, dtype=torch.float64, device=dev)
+    records = torch.empty((1 << 22, 4), dtype=torch.int32, device=dev)
+    counters = torch.zeros(32, dtype=torch.int64, device=dev)
+    reserved = [0]
+    t4 = [out[k].contiguous() for k in ("class", "center", "size", "angle")]
+
+    def entry(name, *extra):
+        def fn():
+            if reserved[0] + B * N > records.shape[0]:
+                reserved[0] = 0
+                counters.zero_()
+            lib.call(name, *[t.data_ptr() for t in t4], gt_box.data_ptr(), gt_id.data_ptr(), counts_t.data_ptr(), thr, kinds, K, roi,
+                     0.0, scratch.data_ptr(), records.data_ptr(), records.shape[0], reserved[0], counters.data_ptr(), 0, B, N, Mmax,
+                     Cn, *extra, stream())
+            reserved[0] += B * N
+        return fn
+
+    no_groups_no_tp = (None, None, None, None, None, None, 0, None, 0, 0, None, 0, 0)
+    e_plain, e_kitti = [], []
+    for _ in range(2):
+        e_plain.append(timed(entry("dpft_dataset_ap_update_f32")))
+        e_kitti.append(timed(entry("dpft_dataset_ap_update_kitti_f32", *no_groups_no_tp)))
+    emit({"what": "update with and without kitti, between device events, each side measured twice (a, b, a, b)",
+          "device": torch.cuda.get_device_name(0), "B": B, "N": N, "C": Cn, "targets": counts, "K": K,
+          "detections_per_update": n_det, "pass1_bits_per_update": n_p1, "pass2_bits_per_update": n_p2, "reps": args.reps,
+          "DatasetAP.update without kitti": t_plain, "DatasetAP.update with kitti": t_kitti,
+          "dpft_dataset_ap_update_f32 alone": e_plain, "dpft_dataset_ap_update_kitti_f32 alone": e_kitti})
+
+    # compute() on ~ --records records: the same batch under new frame numbers
+    plain.reset()
+    kitti.reset()
+    first = 0
+    while plain._bound < args.records * N // max(n_det // B, 1):
+        plain.update(out, labels, first)
+        kitti.update(out, labels, first)
+        first += B
+    torch.cuda.synchronize()
+    walls = {"plain": [], "kitti": []}
+    for _ in range(5):
+        for key, ap in (("plain", plain), ("kitti", kitti)):
+            t0 = time.perf_counter()
+            res = ap.compute()
+            walls[key].append((time.perf_counter() - t0) * 1e3)
+    assert torch.equal(res["ap"].view(torch.int64), plain.compute()["ap"].view(torch.int64))
+
+    # the finalize entries alone, on the sorted records
+    st = kitti.state()
+    rec = DatasetAP.sort_records(st["records"])
+    n = int(rec.shape[0])
+    cls_of = (rec[:, 2] >> 16) & 0xFF
+    start = torch.searchsorted(cls_of.contiguous(), torch.arange(Cn + 1, dtype=cls_of.dtype, device=dev)).to(torch.int64)
+    cells = (Cn - 1) * K
+    buf = torch.empty(cells * (2 + 5 * 41), dtype=torch.float64, device=dev)
+    nthr = torch.empty(cells, dtype=torch.int32, device=dev)
+    o = [0, cells] + [2 * cells + i * 41 * cells for i in range(5)]
+
+    def finalize_plain():
+        lib.call("dpft_dataset_ap_finalize_f64", rec.data_ptr(), n, start.data_ptr(), st["counters"].data_ptr(), Cn, K, 40,
+                 buf[o[0]:].data_ptr(), buf[o[2]:].data_ptr(), buf[o[1]:].data_ptr(), stream())
+
+    def finalize_kitti():
+        lib.call("dpft_dataset_ap_finalize_kitti_f64", rec.data_ptr(), n, start.data_ptr(), st["counters"].data_ptr(), Cn, K,
+                 *[buf[x:].data_ptr() for x in o], nthr.data_ptr(), stream())
+
+    emit({"what": "compute() wall clock, ms, with kitti beside the compute() without on the same records", "records": n,
+          "compute_ms_median without kitti": round(statistics.median(walls["plain"]), 2),
+          "compute_ms_median with kitti": round(statistics.median(walls["kitti"]), 2),
+          "compute_ms_min without kitti": round(min(walls["plain"]), 2), "compute_ms_min with kitti": round(min(walls["kitti"]), 2),
+          "dpft_dataset_ap_finalize_f64 alone": timed(finalize_plain),
+          "dpft_dataset_ap_finalize_kitti_f64 alone (one workgroup per class and combination, three trips)": timed(finalize_kitti),
+          "mAP_3d@0.5": res["mAP_3d@0.5"], "kitti/mAP_3d@0.5": res["kitti/mAP_3d@0.5"], "kitti/mAP11_3d@0.5": res["kitti/mAP11_3d@0.5"],
+          "kitti_nthr": res["kitti_nthr"].tolist()})
 
 
 if __name__ == "__main__":
